@@ -21,6 +21,18 @@ via env FDB_TRAFFIC_BYTES_PER_LAUNCH (collected separately; profiles/), else nul
 cpu_baseline: the CPU oracle (reference-algorithm restatement, kind "port")
 timed on the host cores over a bounded sample of the same workload (N=1 rank 0
 only).
+
+A plain run does only what the headline figure needs: build + upload, warmup,
+the timed steps, the result line. The roofline leg (a HIP-event timing pass of
+its own) and the cpu_baseline leg run only with --full; without it both fields
+are null. --dump-outputs DIR writes what the last timed step left in the
+caller's output buffers as DIR/<name>.npy (float64; buffers above
+DUMP_MAX_ELEMS elements as a fixed seeded sample), so two builds can be
+compared output for output: same arguments, same inputs, same sample. The
+engine marks an empty window or cell with NaN (Prometheus semantics); so that
+every dumped array is finite and comparable by plain subtraction, <name>.npy
+holds 0 at such positions and <name>_nonfinite.npy (float32) says what stood
+there: 0 finite, 1 NaN, 2 +inf, 3 -inf.
 """
 import argparse
 import json
@@ -43,6 +55,12 @@ sys.path.insert(0, REPO)
 import filodb_amd as fdb  # noqa: E402
 
 T0 = 100000  # epoch-ms origin of the synthetic hour
+
+# --dump-outputs: per-array cap (1.5M elements = 12 MB of float64 values + 6 MB
+# of float32 non-finite codes; at most three arrays are written, so a dump
+# stays under 64 MB) and the seed of the sample indices
+DUMP_MAX_ELEMS = 1_500_000
+DUMP_SEED = 20240
 
 WORKLOADS = {
     # BASELINE configs[1]: the headline config
@@ -133,6 +151,30 @@ def cpu_baseline(w, budget_s=12.0):
     }
 
 
+def dump_outputs(dirname, arrays):
+    """Writes each device tensor as <dirname>/<name>.npy (float64). A buffer
+    above DUMP_MAX_ELEMS is written as its values at DUMP_MAX_ELEMS sorted
+    indices drawn from a fixed seed — a function of the buffer length only.
+    Non-finite values are written as 0, and <name>_nonfinite.npy (float32)
+    codes what stood there: 0 finite, 1 NaN, 2 +inf, 3 -inf."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        n = t.numel()
+        if n > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(
+                0, n, DUMP_MAX_ELEMS, dtype=np.int64))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        v = t.cpu().numpy().astype(np.float64, copy=False)
+        code = np.zeros(v.shape, dtype=np.float32)
+        code[np.isnan(v)] = 1
+        code[np.isposinf(v)] = 2
+        code[np.isneginf(v)] = 3
+        np.save(os.path.join(dirname, name + ".npy"),
+                np.where(code == 0, v, 0.0))
+        np.save(os.path.join(dirname, name + "_nonfinite.npy"), code)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -140,6 +182,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="rate_1m", choices=list(WORKLOADS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the roofline timing pass and the "
+                         "cpu_baseline leg (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as "
+                         "DIR/<name>.npy")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", 0))
@@ -155,6 +203,10 @@ def main():
                f"--warmup={args.warmup}", f"--workload={args.workload}"]
         if args.no_cpu_baseline:
             cmd.append("--no-cpu-baseline")
+        if args.full:
+            cmd.append("--full")
+        if args.dump_outputs:
+            cmd.append(f"--dump-outputs={args.dump_outputs}")
         sys.exit(subprocess.run(cmd).returncode)
     n_gpus = max(world, args.gpus)
 
@@ -200,6 +252,7 @@ def main():
 
     is_hist = w["kind"] == "hist"
     nb = w.get("nb", 0)
+    kernel_ms = None   # roofline numerator's time base; measured with --full only
     if is_hist:
         hist_sums = torch.zeros(q.num_groups * nw * nb, dtype=torch.float64,
                                 device=f"cuda:{local_rank}")
@@ -214,12 +267,13 @@ def main():
                            on_device=True)
         for _ in range(args.warmup):
             hist_step()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            hist_step()
-        torch.cuda.synchronize()
-        kernel_ms = (time.perf_counter() - t0) / args.steps * 1000  # sync per call
+        if args.full:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                hist_step()
+            torch.cuda.synchronize()
+            kernel_ms = (time.perf_counter() - t0) / args.steps * 1000  # sync per call
     elif dist is not None and q.agg_id != fdb.AGG_NONE:
         # config #5: the per-shard [G×W] partials merge with ONE collective —
         # RCCL all-reduce over xGMI (ReduceAggregateExec equivalent).
@@ -230,16 +284,20 @@ def main():
             dist.all_reduce(cnt)
         for _ in range(args.warmup):
             agg_step()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        agg_step()
-        torch.cuda.synchronize()
-        kernel_ms = (time.perf_counter() - t0) * 1000
-    else:
+        if args.full:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            agg_step()
+            torch.cuda.synchronize()
+            kernel_ms = (time.perf_counter() - t0) * 1000
+    elif args.full:
         # warmup pass (also yields avg HIP-event kernel ms for the roofline), then
         # wall-time EXACTLY `steps` launches between barriers+synchronize.
         kernel_ms = eng.bench(ds, q, out, out_counts=cnt, on_device=True,
                               warmup=args.warmup, iters=args.steps)
+    elif args.warmup > 0:
+        eng.bench(ds, q, out, out_counts=cnt, on_device=True,
+                  warmup=args.warmup, iters=0)
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
@@ -251,8 +309,8 @@ def main():
         for _ in range(args.steps):
             agg_step()
     else:
-        _ = eng.bench(ds, q, out, out_counts=cnt, on_device=True,
-                      warmup=0, iters=args.steps)
+        eng.bench(ds, q, out, out_counts=cnt, on_device=True,
+                  warmup=0, iters=args.steps)
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
@@ -270,33 +328,46 @@ def main():
     total_samples_per_step = samples_per_step * n_gpus
     value = total_samples_per_step / (ms_per_step / 1000.0)
 
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the timed path receives, as the last step left it
+        if is_hist:
+            arrays = {"bucket_sums": hist_sums, "counts": hist_cnt,
+                      "quantile": hist_quant}
+        elif cnt is not None:
+            arrays = {"out": out, "counts": cnt}
+        else:
+            arrays = {"out": out}
+        dump_outputs(args.dump_outputs, arrays)
+
     if rank == 0:
-        # algorithmic bytes per launch: encoded chunk payload read + output
-        # grid written (directory reads are <1% and omitted)
-        out_bytes = out.numel() * 8 + (cnt.numel() * 8 if cnt is not None else 0)
-        algo_bytes = ds.payload_bytes + out_bytes
-        ach = algo_bytes / (kernel_ms / 1000.0) if kernel_ms > 0 else None
-        traffic = os.environ.get("FDB_TRAFFIC_BYTES_PER_LAUNCH")
-        if not traffic:
-            # PMC-derived HBM bytes per launch, measured by rocprofv3 --pmc
-            # FETCH_SIZE/WRITE_SIZE runs (profiles/; FETCH doubled per the
-            # gfx950 read-side calibration, MI355X_MICROARCH.md §HBM)
-            cal = os.path.join(REPO, "profiles", "traffic_calibration.json")
-            if os.path.exists(cal):
-                with open(cal) as f:
-                    c = json.load(f)
-                traffic = c.get(args.workload)
-        roofline = {
-            "bound": "hbm",
-            "achieved": round(ach / 1e9, 2) if ach else None,
-            "peak": 8000.0,
-            "unit": "GB/s",
-            "frac": round(ach / 8e12, 4) if ach else None,
-            "traffic": float(traffic) if traffic else None,
-        }
+        roofline = None
         cb = None
-        if not args.no_cpu_baseline and n_gpus == 1:
-            cb = cpu_baseline(w)
+        if args.full:
+            # algorithmic bytes per launch: encoded chunk payload read + output
+            # grid written (directory reads are <1% and omitted)
+            out_bytes = out.numel() * 8 + (cnt.numel() * 8 if cnt is not None else 0)
+            algo_bytes = ds.payload_bytes + out_bytes
+            ach = algo_bytes / (kernel_ms / 1000.0) if kernel_ms > 0 else None
+            traffic = os.environ.get("FDB_TRAFFIC_BYTES_PER_LAUNCH")
+            if not traffic:
+                # PMC-derived HBM bytes per launch, measured by rocprofv3 --pmc
+                # FETCH_SIZE/WRITE_SIZE runs (profiles/; FETCH doubled per the
+                # gfx950 read-side calibration noted in profiles/README.md)
+                cal = os.path.join(REPO, "profiles", "traffic_calibration.json")
+                if os.path.exists(cal):
+                    with open(cal) as f:
+                        c = json.load(f)
+                    traffic = c.get(args.workload)
+            roofline = {
+                "bound": "hbm",
+                "achieved": round(ach / 1e9, 2) if ach else None,
+                "peak": 8000.0,
+                "unit": "GB/s",
+                "frac": round(ach / 8e12, 4) if ach else None,
+                "traffic": float(traffic) if traffic else None,
+            }
+            if not args.no_cpu_baseline and n_gpus == 1:
+                cb = cpu_baseline(w)
         line = {
             "metric": "samples/sec scanned+aggregated, 1M series rate()[5m]",
             "value": value,
