@@ -1,15 +1,19 @@
 // Fast scan kernel: the single-chunk-per-series shape (BASELINE configs[1-3]).
 //
-// Ground-up round-2 redesign of the window phase (profiles/README.md round-1
-// findings: the old kernel was latency-bound on per-window search + branchy
-// f64 epilogue chains at 4 waves/SIMD). What changed:
+// One wave per series: decode the chunk into LDS, build the kind's per-row
+// structures (meta), then evaluate 4 windows per lane.
 //
-//  * window row-ranges come from ONE inversion scan over the rows instead of
-//    per-window searches: row i computes two floor-divisions and writes the
-//    window ranges it bounds into sw[]/ew[] (startRow/endRow per window) —
-//    O(rows + windows) total, exact for arbitrary sorted timestamps
-//    (replaces DeltaDeltaDataReader.binarySearch/ceilingIndex on the device;
-//    semantics: WindowedChunkIterator, ChunkSetInfo.scala:467-511)
+//  * each window's row range [startRow, endRow] is computed directly in the
+//    window phase (window_bounds.h): a linear guess from the series' mean
+//    scrape interval, one secant correction, a four-row LDS probe and an
+//    exact integer acceptance test, with a binary search for the rare bound
+//    the probe does not bracket — a short fixed number of independent LDS
+//    reads per bound, exact for arbitrary sorted timestamps (replaces
+//    DeltaDeltaDataReader.binarySearch/ceilingIndex on the device; semantics:
+//    WindowedChunkIterator, ChunkSetInfo.scala:467-511). Earlier designs: a
+//    per-window binary search (~9 dependent LDS reads per bound, round 1) and
+//    a rows→windows inversion scan through per-window LDS arrays (round 2);
+//    profiles/README.md has the measurements.
 //  * timestamps live in LDS as i32 offsets from the chunk's first ts (halves
 //    the LDS footprint and read traffic; chunk span is checked at upload)
 //  * the extrapolatedRate epilogue keeps the oracle's exact operation
@@ -36,12 +40,13 @@
 
 #include "chunk_format.h"
 #include "scan_common.h"
+#include "window_bounds.h"
 #include "../../include/filodb_amd.h"
 
 void fdb_set_error(const char* fmt, ...);   // chunk_builder.cpp
 
 #define FAST_ROWS 400        // reference chunk row cap (filodb-defaults.conf:835)
-#define FAST_TILE 256        // windows per tile (sw/ew LDS arrays)
+#define FAST_TILE 256        // windows per pass: 4 per lane, unrolled
 #define FAST_WAVES 4
 #define FAST_DROPS 32        // sparse counter-reset table capacity
 
@@ -71,8 +76,6 @@ struct FWs {                        // per-wave LDS workspace
   double  grp[KIND == K_MINMAX ? (FAST_ROWS + 7) / 8 : 1];
   int16_t dpos[KIND == K_RATE ? FAST_DROPS : 1];
   double  dcum[KIND == K_RATE ? FAST_DROPS : 1];
-  int16_t sw[FAST_TILE];            // per-window startRow (n = none)
-  int16_t ew[FAST_TILE];            // per-window endRow (-1 = none)
 };
 
 template <int KIND> struct NeedsInv {   // reciprocal table users (AVG/STDDEV;
@@ -104,10 +107,11 @@ __device__ __forceinline__ double f_corr_at(const WS& ws, int dcount, bool dense
 }
 
 // MINW = min waves/SIMD the register allocator must meet. PFX_SQ is
-// LDS-bound at 3 blocks/CU; the group-emit variant carries 12 accumulator
-// registers (4 waves); K_RATE (no reciprocal table, LDS fits 6 blocks/CU) is
-// built at BOTH 5 (96 VGPR, no spills) and 6 (80 VGPR, ~19 spilled) — the
-// launcher picks via FDB_RATE_WAVES, measured on hardware.
+// LDS-bound at 4 blocks/CU; the group-emit variant carries 12 accumulator
+// registers (4 waves); K_RATE (no reciprocal table, LDS fits 7 blocks/CU) is
+// built at 5 (95 VGPR), 6 (80 VGPR, no scratch) and 7 (71 VGPR, 20 B scratch)
+// — the launcher picks via FDB_RATE_WAVES, default 7 as measured on hardware
+// (profiles/README.md, round 3).
 template <int FUNC, int EMIT, int MINW, bool TIMED = false, bool PF = true>
 __global__ __launch_bounds__(FAST_WAVES * 64, MINW)
 void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
@@ -142,7 +146,6 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
     __syncthreads();
   }
 
-  const double inv_step = 1.0 / (double)qstep;
   const double rate_scale = 1000.0 / (double)qwindow;
   const bool qw32 = qwindow < ((int64_t)1 << 31);   // i32 epilogue eligibility
   const double dur_ms = (double)qwindow;
@@ -366,69 +369,47 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
       }
     }
 
+    // per-series constants of the bound search (window_bounds.h): the last
+    // timestamp and the rows-per-ms slope, pinned wave-uniform
+    FdbLin lin;
+    {
+      const int32_t tlast = n > 0 ? ws.tso[n - 1] : 0;
+      lin.last = __builtin_amdgcn_readfirstlane(tlast);
+      lin.inv_h = (n >= 2 && lin.last > 0)
+                      ? (float)(n - 1) / (float)lin.last : 0.0f;
+    }
+    // window w's row range [s, e]: e = last row with ts <= wEnd, s = first
+    // row with ts >= wStart (sentinels e = -1 / s = n when there is none);
+    // t1/t2 are tso[s]/tso[e] as the probe loaded them (valid iff in range)
+    struct WB { int s, e; int32_t t1, t2; };
+    auto window_bounds = [&](int w) {
+      WB b;
+      const int64_t wEndOff = (int64_t)w * qstep - Ae;     // wEnd - ts0
+      b.e = fdb_bound_e(ws.tso, n, lin, wEndOff, &b.t2);
+      b.s = fdb_bound_s(ws.tso, n, lin, wEndOff - qwindow, &b.t1);
+      return b;
+    };
+
     for (int tb = 0; tb < num_windows; tb += FAST_TILE) {
       const int tn = min(FAST_TILE, num_windows - tb);
-      // prefill: no-start sentinel n, no-end sentinel -1
-      for (int i = lane; i < tn; i += 64) { ws.sw[i] = (int16_t)n; ws.ew[i] = -1; }
-      d_wait_lds();
-      __builtin_amdgcn_wave_barrier();
-
-      // ---- inversion scan: rows → window boundaries ------------------------
-      // c_i = first w with wEnd >= ts_i   = ceil((o_i + Ae) / qstep)
-      // d_i = last  w with wStart <= ts_i = floor((o_i + Ae + qwindow) / qstep)
-      // row i ends   windows [c_{i-1}, c_i)   with e = i-1   (wEnd < ts_i)
-      // row i starts windows (d_{i-1}, d_i]   with s = i     (wStart > ts_{i-1})
-      // (a shuffle-free variant recomputing the neighbor boundaries from
-      // ts[i-1] — 4 fdivs/row, no carries — measured SLOWER: the inversion
-      // phase grew 8.2 → 11.1 Gcyc; the shfl form stays)
-      // when qstep | qwindow (the usual Prometheus shape) one division gives
-      // both boundaries: f = floor((o+Ae)/qstep) with its exact mod-zero bit
-      // ⇒ ci = f + (mod != 0) [= ceil], di = f + qwindow/qstep. The wider low
-      // clamp keeps di's derivation exact down to di = -1 (see fdiv_floor_rem).
-      const bool kdiv = (qwindow % qstep) == 0;
-      const int Kwin = kdiv ? (int)(qwindow / qstep) : 0;
-      int c_carry = 0, d_carry = -1;
-      for (int base = 0; base < n; base += 64) {
-        const int i = base + lane;
-        const bool live = i < n;
-        int64_t o = live ? (int64_t)ws.tso[i] : 0;
-        int ci, di;
-        if (kdiv) {             // wave-uniform branch
-          bool nz = false;
-          int f = live ? fdiv_floor_rem(o + Ae, qstep, inv_step, num_windows,
-                                        -1 - Kwin, &nz) : 0;
-          ci = f + (nz ? 1 : 0);
-          di = f + Kwin;
-          if (!live) { ci = 0; di = 0; }
-        } else {
-          ci = live ? fdiv_floor_win(o + Ae + qstep - 1, qstep, inv_step,
-                                     num_windows) : 0;
-          di = live ? fdiv_floor_win(o + Ae + qwindow, qstep, inv_step,
-                                     num_windows) : 0;
+      // the timed variant computes all four windows' bounds ahead of the
+      // window phase so the split can charge them to tI; the sink keeps them
+      // alive although its result stores are suppressed
+      WB tbnd[timing ? 4 : 1];
+      if constexpr (timing) {
+        #pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const int wi = lane + 64 * k;
+          tbnd[k] = WB{1, -1, 0, 0};
+          if (wi < tn) tbnd[k] = window_bounds(tb + wi);
+          asm volatile("" :: "v"(tbnd[k].s ^ tbnd[k].e ^ tbnd[k].t1 ^ tbnd[k].t2));
         }
-        int cprev = __shfl_up(ci, 1);
-        int dprev = __shfl_up(di, 1);
-        if (lane == 0) { cprev = c_carry; dprev = d_carry; }
-        if (live) {
-          if (i > 0) {
-            int lo = max(cprev, tb), hi = min(ci, tb + tn);
-            for (int w = lo; w < hi; w++) ws.ew[w - tb] = (int16_t)(i - 1);
-          }
-          int lo = (i == 0) ? tb : max(dprev + 1, tb);
-          int hi = min(di, tb + tn - 1);
-          for (int w = lo; w <= hi; w++) ws.sw[w - tb] = (int16_t)i;
-        }
-        const int lastl = min(63, n - 1 - base);
-        c_carry = __shfl(ci, lastl);
-        d_carry = __shfl(di, lastl);
+        uint64_t t = __builtin_amdgcn_s_memtime(); tI += t - tt; tt = t;
       }
-      if (n > 0) {          // tail: windows with wEnd >= ts_{n-1} end at n-1
-        for (int w = max(c_carry, tb) + lane; w < tb + tn; w += 64)
-          ws.ew[w - tb] = (int16_t)(n - 1);
-      }
-      d_wait_lds();
-      __builtin_amdgcn_wave_barrier();
-      if (timing) { uint64_t t = __builtin_amdgcn_s_memtime(); tI += t - tt; tt = t; }
+      auto bounds_of = [&](int k, int w, bool wok) {
+        if constexpr (timing) { (void)w; (void)wok; return tbnd[k]; }
+        else { (void)k; return wok ? window_bounds(w) : WB{1, -1, 0, 0}; }
+      };
 
       // ---- window phase: 4 windows per lane --------------------------------
       // results land through emit_res: plain grid store or fastReduce
@@ -477,11 +458,11 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
           const int wi = lane + 64 * k;
           const int w = tb + wi;
           const bool wok = wi < tn;
-          const int s = wok ? ws.sw[wi] : 1;
-          const int e = wok ? ws.ew[wi] : -1;
+          const WB wb = bounds_of(k, w, wok);
+          const int s = wb.s, e = wb.e;
           double res = NAN;
           if (e > s) {
-            const int t1 = ws.tso[s], t2 = ws.tso[e];
+            const int t1 = wb.t1, t2 = wb.t2;   // tso[s], tso[e] from the probe
             if (t2 > t1) {
               double v1 = ws.val[s], v2 = ws.val[e];
               if (IS_COUNTER && dropped) {
@@ -509,8 +490,8 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
         for (int k = 0; k < 4; k++) {
           const int wi = lane + 64 * k;
           const bool wok = wi < tn;
-          const int s = wok ? ws.sw[wi] : 1;
-          const int e = wok ? ws.ew[wi] : -1;
+          const WB wb = bounds_of(k, tb + wi, wok);
+          const int s = wb.s, e = wb.e;
           double res = NAN;
           if (e >= s && e >= 0) {
             double ps = ws.val[e] - (s ? ws.val[s - 1] : 0.0);
@@ -530,8 +511,8 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
         const int wi = lane + 64 * k;
         const int w = tb + wi;
         const bool wok = wi < tn;
-        const int s = wok ? ws.sw[wi] : 0;
-        const int e = wok ? ws.ew[wi] : -1;
+        const WB wb = bounds_of(k, w, wok);
+        const int s = wb.s, e = wb.e;
         double res = NAN;
 
         if constexpr (KIND == K_PFX_SQ) {
@@ -569,8 +550,10 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
             res = (double)((int)ws.cnt[e] - (int)ws.cnt[s]);
         } else {  // K_LAST family
           if constexpr (FUNC == FN_TIMESTAMP) {
-            // TimestampChunkedFunction: no window-start bound; seconds
-            if (wok && e >= 0) res = (double)(ts0 + ws.tso[e]) / 1000.0;
+            // TimestampChunkedFunction: no window-start bound on the row, but
+            // WindowedChunkIterator drops a chunk that ends before wStart
+            // (s == n), so such a window has no sample at all; seconds
+            if (wok && e >= 0 && s < n) res = (double)(ts0 + wb.t2) / 1000.0;
           } else if constexpr (FUNC == FN_PRESENT) {
             if (wok && e >= s && e >= 0) {
               double v = ws.val[e];
@@ -656,7 +639,7 @@ int32_t fdb_launch_fast_scan(hipStream_t stream, const uint8_t* blob, DirSoA dir
   if (const char* g = getenv("FDB_GRID")) cap = atoi(g);   // perf experiments
   if (cap > 0 && grid > cap) grid = cap;
   const char* rw = getenv("FDB_RATE_WAVES");   // occupancy experiment knob
-  const int rate_w = rw ? atoi(rw) : 6;   // 6-wave prefetch-free measured best (2.48 vs 2.62 ms)
+  const int rate_w = rw ? atoi(rw) : 7;   // 7-wave prefetch-free measured best (2.03 vs 2.07 ms at 6)
   #define FARGS blob, dir, series_first, series_nchunks, group_ids, \
       series_by_group, num_series, qstart, qstep, qwindow, num_windows, \
       agg_id, out, out_cnt, out_sq, phase_mask
@@ -673,6 +656,9 @@ int32_t fdb_launch_fast_scan(hipStream_t stream, const uint8_t* blob, DirSoA dir
                                          stream, FARGS);
       else if (rate_w == 6)   // 6 waves/SIMD: prefetch stripped (register diet)
         hipLaunchKernelGGL((fast_scan_kernel<FN_RATE, 0, 6, false, false>),
+                           dim3(grid), dim3(FAST_WAVES * 64), 0, stream, FARGS);
+      else if (rate_w == 7)   // LDS fits 7 blocks/CU; needs <= 72 VGPRs
+        hipLaunchKernelGGL((fast_scan_kernel<FN_RATE, 0, 7, false, false>),
                            dim3(grid), dim3(FAST_WAVES * 64), 0, stream, FARGS);
       else LAUNCH(FN_RATE, 0, 5);
       break;

@@ -1,0 +1,125 @@
+// Window row bounds over one chunk's sorted timestamp offsets: for a time
+// offset x (relative to the chunk's first timestamp, like tso[])
+//
+//   fdb_bound_e(x) = largest  row i with tso[i] <= x, or -1 if there is none
+//   fdb_bound_s(y) = smallest row i with tso[i] >= y, or  n if there is none
+//
+// (WindowedChunkIterator's endRow/startRow, ChunkSetInfo.scala:467-511; rows
+// with equal timestamps resolve to the largest index for e and the smallest
+// for s.) For integer timestamps s(y) = e(y - 1) + 1, so one search serves both.
+//
+// Scrape timestamps are close to linear in the row index, so a bound is found
+// by a linear guess, one secant correction from the guessed row's own
+// timestamp, and a four-row probe around the corrected guess: a short fixed
+// number of independent reads instead of a dependent binary-search chain. The
+// floating-point arithmetic only steers the guess; the result is accepted on
+// an exact integer predicate over the probed rows, and a bound the probe does
+// not bracket falls back to a plain binary search (the "residue" path), so
+// the answer is exact for ANY sorted tso[].
+//
+// Compiles as device code under hipcc and as plain host C++ (no HIP runtime
+// needed) — tools/verify_window_bounds.cpp checks it against a linear scan.
+//
+// Contract: tso[0..n) sorted ascending with tso[0] >= 0, and the array has at
+// least 4 readable elements whatever n is (the probe reads a clamped 4-row
+// span; elements at index >= n are read but never interpreted).
+#ifndef FDB_WINDOW_BOUNDS_H
+#define FDB_WINDOW_BOUNDS_H
+
+#include <cstdint>
+
+#ifdef __HIPCC__
+#define FDB_HD __host__ __device__
+#else
+#define FDB_HD
+#endif
+
+// per-series constants of the linear guess, computed once per series
+// (wave-uniform on the device): the last timestamp and the rows-per-unit-time
+// slope. The slope is 0 for a degenerate span — every guess is then row 0 and
+// the probe/residue path does the work.
+struct FdbLin {
+  int32_t last;     // tso[n-1], 0 when n == 0
+  float inv_h;      // (n-1) / tso[n-1], 0 when n < 2 or tso[n-1] == 0
+};
+
+FDB_HD inline FdbLin fdb_bounds_prepare(const int32_t* tso, int n) {
+  FdbLin lin;
+  lin.last = n > 0 ? tso[n - 1] : 0;
+  lin.inv_h = (n >= 2 && lin.last > 0) ? (float)(n - 1) / (float)lin.last : 0.0f;
+  return lin;
+}
+
+// residue path: largest i in [-1, n) with tso[i] <= x (<= 9 steps at n <= 400)
+FDB_HD inline int fdb_bound_search(const int32_t* tso, int n, int32_t x) {
+  int lo = 0, hi = n;            // invariant: tso[<lo] <= x < tso[>=hi]
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (tso[mid] <= x) lo = mid + 1; else hi = mid;
+  }
+  return lo - 1;
+}
+
+// e(x) plus the timestamps the probe already holds: *t_e = tso[e] when e >= 0,
+// *t_next = tso[e+1] when e+1 < n (unspecified otherwise). `residue`, when
+// non-null, is incremented if the binary-search fallback ran.
+FDB_HD inline int fdb_bound_core(const int32_t* tso, int n, FdbLin lin,
+                                 int64_t x, int32_t* t_e, int32_t* t_next,
+                                 int* residue) {
+  // clamp in i64 before narrowing: x may lie far outside the chunk. e(x) is
+  // constant below -1 and above the last timestamp, so the clamp is exact.
+  const float inv_h = lin.inv_h;
+  int64_t xl = x < -1 ? -1 : x;
+  if (xl > lin.last) xl = lin.last;
+  const int32_t xc = (int32_t)xl;
+  const int top = n > 0 ? n - 1 : 0;
+
+  // linear guess, then one secant step from the guessed row's timestamp
+  // (differences via unsigned wrap: they only steer, never decide)
+  int g = (int)((float)xc * inv_h);
+  g = g < 0 ? 0 : (g > top ? top : g);
+  const int32_t d = (int32_t)((uint32_t)xc - (uint32_t)tso[g]);
+  g += (int)__builtin_floorf((float)d * inv_h);
+  g = g < 0 ? 0 : (g > top ? top : g);
+
+  // probe rows b0..b0+3 (covers g-1..g+2 away from the ends); le_k says
+  // "row b0+k exists and is <= x", non-increasing in k for sorted input
+  const int bmax = n > 4 ? n - 4 : 0;
+  int b0 = g - 1;
+  b0 = b0 < 0 ? 0 : (b0 > bmax ? bmax : b0);
+  const int32_t v0 = tso[b0], v1 = tso[b0 + 1], v2 = tso[b0 + 2], v3 = tso[b0 + 3];
+  const bool le0 = b0 < n && v0 <= xc;
+  const bool le1 = b0 + 1 < n && v1 <= xc;
+  const bool le2 = b0 + 2 < n && v2 <= xc;
+  const bool le3 = b0 + 3 < n && v3 <= xc;
+  const int c = (int)le0 + (int)le1 + (int)le2 + (int)le3;
+  int e = b0 - 1 + c;
+  // exact acceptance: the row below the span is <= x (or there is none), and
+  // the row above e is > x (or e is the last row)
+  const bool ok = (le0 || b0 == 0) && (!le3 || b0 + 3 >= n - 1);
+  *t_e = c == 1 ? v0 : (c == 2 ? v1 : (c == 3 ? v2 : v3));
+  *t_next = c == 0 ? v0 : (c == 1 ? v1 : (c == 2 ? v2 : v3));
+  if (!ok) {
+    e = fdb_bound_search(tso, n, xc);
+    if (e >= 0) *t_e = tso[e];
+    if (e + 1 < n) *t_next = tso[e + 1];
+    if (residue) ++*residue;
+  }
+  return e;
+}
+
+// endRow: largest i with tso[i] <= x (-1 = none); *t = tso[e] when e >= 0
+FDB_HD inline int fdb_bound_e(const int32_t* tso, int n, FdbLin lin, int64_t x,
+                              int32_t* t, int* residue = nullptr) {
+  int32_t unused;
+  return fdb_bound_core(tso, n, lin, x, t, &unused, residue);
+}
+
+// startRow: smallest i with tso[i] >= y (n = none); *t = tso[s] when s < n
+FDB_HD inline int fdb_bound_s(const int32_t* tso, int n, FdbLin lin, int64_t y,
+                              int32_t* t, int* residue = nullptr) {
+  int32_t unused;
+  return fdb_bound_core(tso, n, lin, y - 1, &unused, t, residue) + 1;
+}
+
+#endif  // FDB_WINDOW_BOUNDS_H

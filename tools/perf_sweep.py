@@ -43,11 +43,11 @@ def main():
     gout = torch.empty(1000 * nw, dtype=torch.float64, device="cuda:0")
     gcnt = torch.empty_like(gout)
 
-    for waves in ("6", "5"):
+    for waves in ("7", "6", "5"):
         os.environ["FDB_RATE_WAVES"] = waves
         ms = bench(eng, ds, q_rate, out)
         print(f"rate waves={waves}: {ms:.3f} ms", flush=True)
-    os.environ["FDB_RATE_WAVES"] = "6"
+    os.environ.pop("FDB_RATE_WAVES")      # back to the launcher's default
     for gridcap in ("1536", "3072", "16384"):
         os.environ["FDB_GRID"] = gridcap
         ms = bench(eng, ds, q_rate, out)
@@ -59,14 +59,13 @@ def main():
         print(f"sum-by-group fused={fused}: {ms:.3f} ms", flush=True)
     os.environ.pop("FDB_FUSED_GROUP")
     # phase split (s_memtime; pm bit 3 clobbers out[] with per-wave cycles)
-    os.environ["FDB_RATE_WAVES"] = "6"
     q_rate._pad = 8
     eng.query(ds, q_rate, out=out, on_device=True)
     eng.synchronize()
     nwaves = 8192 * 4
     ph = out[:nwaves * 4].reshape(nwaves, 4).cpu().numpy()
     tot = ph.sum(axis=0)
-    names = ["decode", "meta", "inversion", "windows"]
+    names = ["decode", "meta", "bounds", "windows"]
     print("rate phase split:",
           " ".join(f"{nm}={v / tot.sum() * 100:.0f}%" for nm, v in zip(names, tot)),
           f"(sum {tot.sum() / 1e9:.2f} Gcyc over {nwaves} waves)", flush=True)
