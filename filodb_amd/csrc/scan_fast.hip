@@ -14,6 +14,14 @@
 //    per-window binary search (~9 dependent LDS reads per bound, round 1) and
 //    a rows→windows inversion scan through per-window LDS arrays (round 2);
 //    profiles/README.md has the measurements.
+//  * when the query window is m = 1..64 whole steps (rate()[5m] at step 15 s:
+//    m = 20), window w starts at the offset where window w-m ends, so the
+//    SHARE instantiations search only each window's END: the start row at
+//    that same offset follows from what the probe already holds
+//    (fdb_bound_s_from_e: no read, or one read when a row sits exactly on
+//    the edge) and travels to the lane that owns window w+m through one
+//    ds_bpermute — five searches per lane and tile instead of eight, no LDS
+//    array. Any other window/step pair keeps two searches per window.
 //  * timestamps live in LDS as i32 offsets from the chunk's first ts (halves
 //    the LDS footprint and read traffic; chunk span is checked at upload)
 //  * the extrapolatedRate epilogue keeps the oracle's exact operation
@@ -68,7 +76,8 @@ template <int FUNC> struct FKind { static constexpr int v =
 
 template <int KIND>
 struct FWs {                        // per-wave LDS workspace
-  int32_t tso[FAST_ROWS];           // ts - ts0 (i32 offsets)
+  int32_t tso[FAST_ROWS + 4];       // ts - ts0 (i32 offsets); the pad keeps
+                                    // tso[startRow] readable at startRow == n
   double  val[FAST_ROWS];           // raw values, or prefix sums (PFX kinds)
   uint16_t cnt[(KIND == K_PFX || KIND == K_PFX_SQ || KIND == K_CHANGES)
                    ? FAST_ROWS : 1];
@@ -109,10 +118,16 @@ __device__ __forceinline__ double f_corr_at(const WS& ws, int dcount, bool dense
 // MINW = min waves/SIMD the register allocator must meet. PFX_SQ is
 // LDS-bound at 4 blocks/CU; the group-emit variant carries 12 accumulator
 // registers (4 waves); K_RATE (no reciprocal table, LDS fits 7 blocks/CU) is
-// built at 5 (95 VGPR), 6 (80 VGPR, no scratch) and 7 (71 VGPR, 20 B scratch)
-// — the launcher picks via FDB_RATE_WAVES, default 7 as measured on hardware
-// (profiles/README.md, round 3).
-template <int FUNC, int EMIT, int MINW, bool TIMED = false, bool PF = true>
+// built at 5 (95 VGPR), 6 (80 VGPR) and 7 (72 VGPR, 20 B scratch with the
+// shared search) — the launcher picks via FDB_RATE_WAVES, default 7 as
+// measured on hardware (profiles/README.md, rounds 3 and 4). The gauge kinds
+// are built at 6: the shared search needs ~10 more VGPRs than the 79 they had,
+// and the bound keeps their sixth wave/SIMD (AVG: 80 VGPR, 12 B scratch). SHARE selects the shared window search
+// (window = 1..64 whole steps; wshare carries that ratio): a template
+// parameter, not a runtime branch — with both searches in one kernel the
+// 79-VGPR gauge kinds grew to 87 and lost their sixth wave/SIMD.
+template <int FUNC, int EMIT, int MINW, bool TIMED = false, bool PF = true,
+          bool SHARE = false>
 __global__ __launch_bounds__(FAST_WAVES * 64, MINW)
 void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
                       const int32_t* __restrict__ series_first,
@@ -125,7 +140,8 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
                       double* __restrict__ out,
                       double* __restrict__ out_cnt,
                       double* __restrict__ out_sq,
-                      int pm)    // bit 3: s_memtime phase split into out[]
+                      int pm,    // bit 3: s_memtime phase split into out[]
+                      int wshare)   // SHARE: m = qwindow/qstep, 1..64
 {
   constexpr int KIND = FKind<FUNC>::v;
   constexpr bool IS_COUNTER = (FUNC == FN_RATE || FUNC == FN_INCREASE);
@@ -389,9 +405,57 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
       b.s = fdb_bound_s(ws.tso, n, lin, wEndOff - qwindow, &b.t1);
       return b;
     };
+    // shared search (wshare = m, window = m steps): window w starts at the
+    // offset where window w-m ends, so each lane searches only its windows'
+    // ENDS, derives the start row AT that same offset from what the probe
+    // already holds (fdb_bound_s_from_e) and hands it to the lane that owns
+    // window w+m. Windows sit at lane + 64k, so w-m is lane (lane-m)&63 of
+    // this slot when lane >= m and of the previous slot otherwise: the sender
+    // picks by lane < 64-m, one ds_bpermute delivers, and only the previous
+    // slot's start row stays live. Five searches per lane instead of eight:
+    // four ends plus the seed for the windows before the first tile.
+    auto end_search = [&](int w, int32_t* t2, int* s_at_end) {
+      const int64_t x = (int64_t)w * qstep - Ae;           // wEnd - ts0
+      int32_t t_next, unused;
+      const int e = fdb_bound_core(ws.tso, n, lin, x, t2, &t_next, nullptr);
+      *s_at_end = fdb_bound_s_from_e(ws.tso, n, lin, x, e, *t2, t_next, &unused);
+      return e;
+    };
+    const int share_src = ((lane - wshare) & 63) << 2;     // bpermute address
+    int s_prev = 0;         // start row at the end of this lane's window in
+                            // the previous slot; slot -1 = windows -64..-1
+    if constexpr (SHARE) {
+      int32_t unused;
+      end_search(lane - 64, &unused, &s_prev);
+    }
+    // every lane of the wave calls this (the exchange needs its senders)
+    auto shared_bounds = [&](int w) {
+      WB b;
+      int s_cur;
+      b.e = end_search(w, &b.t2, &s_cur);
+      b.s = __builtin_amdgcn_ds_bpermute(share_src,
+                                         lane < 64 - wshare ? s_cur : s_prev);
+      s_prev = s_cur;
+      b.t1 = ws.tso[b.s];     // 0 <= s <= n; tso[n] is readable, never used
+      return b;
+    };
 
     for (int tb = 0; tb < num_windows; tb += FAST_TILE) {
       const int tn = min(FAST_TILE, num_windows - tb);
+      // slot k's bounds; slots run in order k = 0..3 (the shared search hands
+      // slot k-1 on to slot k, and slot 3 on to the next tile's slot 0)
+      auto calc_bounds = [&](int k, int w, bool wok) {
+        WB b = WB{1, -1, 0, 0};
+        if constexpr (SHARE) {
+          if (64 * k < tn) {             // wave-uniform: the slot has windows
+            const WB sb = shared_bounds(w);
+            if (wok) b = sb;
+          }
+        } else if (wok) {
+          b = window_bounds(w);
+        }
+        return b;
+      };
       // the timed variant computes all four windows' bounds ahead of the
       // window phase so the split can charge them to tI; the sink keeps them
       // alive although its result stores are suppressed
@@ -400,15 +464,14 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
         #pragma unroll
         for (int k = 0; k < 4; k++) {
           const int wi = lane + 64 * k;
-          tbnd[k] = WB{1, -1, 0, 0};
-          if (wi < tn) tbnd[k] = window_bounds(tb + wi);
+          tbnd[k] = calc_bounds(k, tb + wi, wi < tn);
           asm volatile("" :: "v"(tbnd[k].s ^ tbnd[k].e ^ tbnd[k].t1 ^ tbnd[k].t2));
         }
         uint64_t t = __builtin_amdgcn_s_memtime(); tI += t - tt; tt = t;
       }
       auto bounds_of = [&](int k, int w, bool wok) {
         if constexpr (timing) { (void)w; (void)wok; return tbnd[k]; }
-        else { (void)k; return wok ? window_bounds(w) : WB{1, -1, 0, 0}; }
+        else return calc_bounds(k, w, wok);
       };
 
       // ---- window phase: 4 windows per lane --------------------------------
@@ -640,46 +703,53 @@ int32_t fdb_launch_fast_scan(hipStream_t stream, const uint8_t* blob, DirSoA dir
   if (cap > 0 && grid > cap) grid = cap;
   const char* rw = getenv("FDB_RATE_WAVES");   // occupancy experiment knob
   const int rate_w = rw ? atoi(rw) : 7;   // 7-wave prefetch-free measured best (2.03 vs 2.07 ms at 6)
+  // windows share end searches when the window is m = 1..64 whole steps
+  // (FDB_WINDOW_SHARE=0: the two-searches-per-window path, for A/B runs)
+  int wshare = 0;
+  if (qstep > 0 && qwindow % qstep == 0 && qwindow / qstep >= 1 &&
+      qwindow / qstep <= 64)
+    wshare = (int)(qwindow / qstep);
+  if (const char* s = getenv("FDB_WINDOW_SHARE")) { if (atoi(s) == 0) wshare = 0; }
+  // one launch of <F, EMIT, MINW, TIMED, PF>, SHARE picked by wshare
+  #define LAUNCH5(F, E, W, T, P) do { \
+    if (wshare) hipLaunchKernelGGL((fast_scan_kernel<F, E, W, T, P, true>), \
+        dim3(grid), dim3(FAST_WAVES * 64), 0, stream, FARGS); \
+    else hipLaunchKernelGGL((fast_scan_kernel<F, E, W, T, P, false>), \
+        dim3(grid), dim3(FAST_WAVES * 64), 0, stream, FARGS); } while (0)
   #define FARGS blob, dir, series_first, series_nchunks, group_ids, \
       series_by_group, num_series, qstart, qstep, qwindow, num_windows, \
-      agg_id, out, out_cnt, out_sq, phase_mask
-  #define LAUNCH(F, E, W) hipLaunchKernelGGL((fast_scan_kernel<F, E, W>), \
-      dim3(grid), dim3(FAST_WAVES * 64), 0, stream, FARGS)
+      agg_id, out, out_cnt, out_sq, phase_mask, wshare
+  #define LAUNCH(F, E, W) LAUNCH5(F, E, W, false, true)
   #define FCASE(F, W) case F: \
     if (emit_group) LAUNCH(F, 1, 4); else LAUNCH(F, 0, W); break
   const bool timed = (phase_mask & 8) != 0;   // s_memtime phase ablation
   switch (func_id) {
     case FN_RATE:
       if (emit_group) LAUNCH(FN_RATE, 1, 4);
-      else if (timed) hipLaunchKernelGGL((fast_scan_kernel<FN_RATE, 0, 5, true>),
-                                         dim3(grid), dim3(FAST_WAVES * 64), 0,
-                                         stream, FARGS);
+      else if (timed) LAUNCH5(FN_RATE, 0, 5, true, true);
       else if (rate_w == 6)   // 6 waves/SIMD: prefetch stripped (register diet)
-        hipLaunchKernelGGL((fast_scan_kernel<FN_RATE, 0, 6, false, false>),
-                           dim3(grid), dim3(FAST_WAVES * 64), 0, stream, FARGS);
+        LAUNCH5(FN_RATE, 0, 6, false, false);
       else if (rate_w == 7)   // LDS fits 7 blocks/CU; needs <= 72 VGPRs
-        hipLaunchKernelGGL((fast_scan_kernel<FN_RATE, 0, 7, false, false>),
-                           dim3(grid), dim3(FAST_WAVES * 64), 0, stream, FARGS);
+        LAUNCH5(FN_RATE, 0, 7, false, false);
       else LAUNCH(FN_RATE, 0, 5);
       break;
     case FN_AVG:
       if (emit_group) LAUNCH(FN_AVG, 1, 4);
-      else if (timed) hipLaunchKernelGGL((fast_scan_kernel<FN_AVG, 0, 5, true>),
-                                         dim3(grid), dim3(FAST_WAVES * 64), 0,
-                                         stream, FARGS);
-      else LAUNCH(FN_AVG, 0, 5);
+      else if (timed) LAUNCH5(FN_AVG, 0, 5, true, true);
+      else LAUNCH(FN_AVG, 0, 6);
       break;
-    FCASE(FN_INCREASE, 6); FCASE(FN_DELTA, 6); FCASE(FN_SUM, 5);
-    FCASE(FN_COUNT, 5); FCASE(FN_RATE_OVER_DELTA, 5);
-    FCASE(FN_MIN, 5); FCASE(FN_MAX, 5); FCASE(FN_STDDEV, 3); FCASE(FN_STDVAR, 3);
-    FCASE(FN_CHANGES, 5); FCASE(FN_LAST, 5); FCASE(FN_PRESENT, 5);
-    FCASE(FN_TIMESTAMP, 5); FCASE(FN_ZSCORE, 5);
+    FCASE(FN_INCREASE, 6); FCASE(FN_DELTA, 6); FCASE(FN_SUM, 6);
+    FCASE(FN_COUNT, 6); FCASE(FN_RATE_OVER_DELTA, 6);
+    FCASE(FN_MIN, 6); FCASE(FN_MAX, 6); FCASE(FN_STDDEV, 3); FCASE(FN_STDVAR, 3);
+    FCASE(FN_CHANGES, 6); FCASE(FN_LAST, 6); FCASE(FN_PRESENT, 6);
+    FCASE(FN_TIMESTAMP, 6); FCASE(FN_ZSCORE, 6);
     default:
       fdb_set_error("fast scan: unsupported func_id %d", func_id);
       return FDB_ERR_BADARG;
   }
   #undef FCASE
   #undef LAUNCH
+  #undef LAUNCH5
   #undef FARGS
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {

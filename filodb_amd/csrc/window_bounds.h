@@ -7,6 +7,10 @@
 // (WindowedChunkIterator's endRow/startRow, ChunkSetInfo.scala:467-511; rows
 // with equal timestamps resolve to the largest index for e and the smallest
 // for s.) For integer timestamps s(y) = e(y - 1) + 1, so one search serves both.
+// And s(y) follows from the end search at the SAME offset, e(y), with at most
+// one extra read (fdb_bound_s_from_e): where the query window is a whole
+// number of steps, a window's start offset is an earlier window's end offset,
+// and the start search is not repeated at all.
 //
 // Scrape timestamps are close to linear in the row index, so a bound is found
 // by a linear guess, one secant correction from the guessed row's own
@@ -120,6 +124,37 @@ FDB_HD inline int fdb_bound_s(const int32_t* tso, int n, FdbLin lin, int64_t y,
                               int32_t* t, int* residue = nullptr) {
   int32_t unused;
   return fdb_bound_core(tso, n, lin, y - 1, &unused, t, residue) + 1;
+}
+
+// startRow at offset y from the END search at the same offset: E = e(y),
+// t_e = tso[E] (valid when E >= 0), t_next = tso[E+1] (valid when E+1 < n),
+// exactly as fdb_bound_core hands them back. Returns s(y), the smallest row
+// with tso >= y (n = none); *t1 = tso[s] when s < n.
+//
+//   no row sits exactly on y (E < 0 or t_e != y): every row up to E is < y,
+//     so s = E + 1 and tso[s] = t_next — no memory access at all
+//   t_e == y, and row E-1 is smaller (or E == 0): s = E — one read
+//   t_e == y inside a run of equal timestamps: the run's first row, by the
+//     full search (fdb_bound_s)
+//
+// The fast scan kernel uses this to share searches between windows: when the
+// window length is m query steps, window w starts where window w-m ends, so
+// w's start row follows from the end search w-m already did.
+FDB_HD inline int fdb_bound_s_from_e(const int32_t* tso, int n, FdbLin lin,
+                                     int64_t y, int E, int32_t t_e,
+                                     int32_t t_next, int32_t* t1,
+                                     int* residue = nullptr) {
+  int s = E + 1;
+  *t1 = t_next;
+  if (E >= 0 && (int64_t)t_e == y) {
+    if (E == 0 || tso[E - 1] < t_e) {
+      s = E;
+      *t1 = t_e;
+    } else {
+      s = fdb_bound_s(tso, n, lin, y, t1, residue);
+    }
+  }
+  return s;
 }
 
 #endif  // FDB_WINDOW_BOUNDS_H

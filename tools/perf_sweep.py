@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Perf sweep on one resident dataset: builds the headline (configs[1]) store
 once, then times kernel variants toggled by env knobs — avoids paying the
-host-side synth build per variant. Run on a GPU box via gpurun."""
+host-side synth build per variant. `--split-only` stops after the rate
+timings and the in-kernel phase split (no gauge or histogram stores)."""
 import os
 import sys
 import time
@@ -62,7 +63,7 @@ def main():
     q_rate._pad = 8
     eng.query(ds, q_rate, out=out, on_device=True)
     eng.synchronize()
-    nwaves = 8192 * 4
+    nwaves = min((n + 3) // 4, 16384) * 4     # the launcher's grid x 4 waves
     ph = out[:nwaves * 4].reshape(nwaves, 4).cpu().numpy()
     tot = ph.sum(axis=0)
     names = ["decode", "meta", "bounds", "windows"]
@@ -70,6 +71,8 @@ def main():
           " ".join(f"{nm}={v / tot.sum() * 100:.0f}%" for nm, v in zip(names, tot)),
           f"(sum {tot.sum() / 1e9:.2f} Gcyc over {nwaves} waves)", flush=True)
     q_rate._pad = 0
+    if "--split-only" in sys.argv[1:]:
+        return
 
     # gauge workload on the same box (separate store: raw f64 values)
     del ds
