@@ -25,6 +25,8 @@ FN_QUANTILE_OVER_TIME, FN_MAD_OVER_TIME = 16, 17
 FN_PREDICT_LINEAR = 18
 FN_RATE_OVER_DELTA = 19
 FN_HOLT_WINTERS = 20
+# instant range functions (RangeFunction.scala:489-494, RangeInstantFunctions.scala)
+FN_IRATE, FN_IDELTA, FN_RESETS, FN_DERIV = 21, 22, 23, 24
 # aggregation ids (RowAggregator implementations)
 AGG_NONE, AGG_SUM, AGG_COUNT, AGG_MIN, AGG_MAX, AGG_AVG = 0, 1, 2, 3, 4, 5
 AGG_TOPK, AGG_BOTTOMK = 6, 7

@@ -728,8 +728,11 @@ extern "C" fdb_dataset_t* fdb_dataset_upload(fdb_engine_t* e, const fdb_store_t*
     return nullptr;
   }
   // chunk summaries for the streaming walk (query-independent; skipped when
-  // every series takes the single-chunk fast path)
-  if (has_scalar && !d->fast_ok) {
+  // every series takes the single-chunk fast path; FDB_FAST=0 at upload keeps
+  // them, so the same dataset can be walked by the general path for A/B runs)
+  const char* fenv = getenv("FDB_FAST");
+  const bool fast_off = fenv && atoi(fenv) == 0;
+  if (has_scalar && (!d->fast_ok || fast_off)) {
     if (hipMalloc(&d->sums, (size_t)fdb_chunksum_bytes(nc)) != hipSuccess) {
       fdb_set_error("summary allocation failed (out of HBM?)");
       fdb_dataset_destroy(d);

@@ -72,7 +72,8 @@ template <int FUNC> struct FKind { static constexpr int v =
      FUNC == FN_RATE_OVER_DELTA) ? K_PFX :
     (FUNC == FN_STDDEV || FUNC == FN_STDVAR) ? K_PFX_SQ :
     (FUNC == FN_MIN || FUNC == FN_MAX) ? K_MINMAX :
-    (FUNC == FN_CHANGES) ? K_CHANGES : K_LAST; };
+    (FUNC == FN_CHANGES || FUNC == FN_RESETS) ? K_CHANGES :
+    K_LAST; };   // incl. FN_IRATE / FN_IDELTA: the window's last two raw rows
 
 template <int KIND>
 struct FWs {                        // per-wave LDS workspace
@@ -357,6 +358,10 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
       }
     }
     if constexpr (KIND == K_CHANGES) {
+      // adjacent-pair indicator prefix: x != px (changes) or x < px (resets,
+      // ResetsFunction RangeInstantFunctions.scala:352-375); a NaN on either
+      // side never counts
+      constexpr bool IS_RESETS = (FUNC == FN_RESETS);
       int ccarry = 0;
       double carry_x = NAN;
       for (int base = 0; base < n; base += 64) {
@@ -364,7 +369,8 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
         double x = (i < n) ? ws.val[i] : NAN;
         double px = __shfl_up(x, 1);
         if (lane == 0) px = carry_x;
-        int ind = (i > 0 && i < n && !isnan(x) && !isnan(px) && x != px) ? 1 : 0;
+        int ind = (i > 0 && i < n && !isnan(x) && !isnan(px) &&
+                   (IS_RESETS ? x < px : x != px)) ? 1 : 0;
         int s = wave_incl_scan_i(ind, lane);
         if (i < n) ws.cnt[i] = (uint16_t)(ccarry + s);
         ccarry += __shfl(s, 63);
@@ -608,7 +614,8 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
             res = mm;
           }
         } else if constexpr (KIND == K_CHANGES) {
-          // single chunk: change-indicator prefix over (s, e]; prev starts NaN
+          // single chunk: indicator prefix over (s, e]; prev starts NaN.
+          // resets: same shape, an empty window stays NaN
           if (wok && e >= s && e >= 0)
             res = (double)((int)ws.cnt[e] - (int)ws.cnt[s]);
         } else {  // K_LAST family
@@ -626,6 +633,26 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
           } else if constexpr (FUNC == FN_LAST) {
             // ts[e] >= ts[s] >= wStart holds whenever the range is nonempty
             if (wok && e >= s && e >= 0) res = ws.val[e];
+          } else if constexpr (FUNC == FN_IRATE || FUNC == FN_IDELTA) {
+            // instantValue (RangeInstantFunctions.scala:68-95) on the
+            // window's last two rows; e > s means at least two rows, e >= 1.
+            // irate: IRateFunction reads counter-corrected rows
+            // (BufferableCounterCorrectionIterator: NaN -> 0, a drop adds the
+            // previous value to a running correction); the correction common
+            // to both rows cancels, leaving last on a drop and last - prev
+            // otherwise. One divide, then one multiply.
+            if (wok && e > s) {
+              double last = ws.val[e], prev = ws.val[e - 1];
+              if constexpr (FUNC == FN_IDELTA) {
+                res = last - prev;
+              } else {
+                if (isnan(last)) last = 0;
+                if (isnan(prev)) prev = 0;
+                const double d = (last < prev) ? last : last - prev;
+                const double dt = (double)(wb.t2 - ws.tso[e - 1]);
+                res = (dt == 0) ? NAN : d / dt * 1000.0;
+              }
+            }
           } else {  // FN_ZSCORE (AggrOverTimeFunctions.scala:1592-1603)
             if (wok && e >= s && e >= 0) {
               double sm = NAN, sq = NAN, lastv = NAN;
@@ -682,6 +709,7 @@ bool fdb_fast_scan_supported(int func_id) {
     case FN_MIN: case FN_MAX: case FN_STDDEV: case FN_STDVAR:
     case FN_CHANGES: case FN_LAST: case FN_PRESENT: case FN_TIMESTAMP:
     case FN_ZSCORE:
+    case FN_IRATE: case FN_IDELTA: case FN_RESETS:
       return true;
     default:
       return false;
@@ -743,6 +771,12 @@ int32_t fdb_launch_fast_scan(hipStream_t stream, const uint8_t* blob, DirSoA dir
     FCASE(FN_MIN, 6); FCASE(FN_MAX, 6); FCASE(FN_STDDEV, 3); FCASE(FN_STDVAR, 3);
     FCASE(FN_CHANGES, 6); FCASE(FN_LAST, 6); FCASE(FN_PRESENT, 6);
     FCASE(FN_TIMESTAMP, 6); FCASE(FN_ZSCORE, 6);
+    FCASE(FN_IRATE, 6); FCASE(FN_IDELTA, 6);
+    case FN_RESETS:   // prefetch-free like the 6/7-wave rate builds: with the
+      // prefetch registers the shared search spills 2 VGPRs at 6 waves/SIMD
+      if (emit_group) LAUNCH(FN_RESETS, 1, 4);
+      else LAUNCH5(FN_RESETS, 0, 6, false, false);
+      break;
     default:
       fdb_set_error("fast scan: unsupported func_id %d", func_id);
       return FDB_ERR_BADARG;

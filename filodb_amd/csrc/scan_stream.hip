@@ -5,7 +5,7 @@
 //
 //  * summary_kernel (once per dataset upload, one wave per chunk): decodes
 //    each chunk into LDS and reduces it to a 192-B ChunkSum — totals
-//    (sum/sumsq/count/min/max/interior-changes), boundary values, the
+//    (sum/sumsq/count/min/max/interior-changes/interior-resets), boundary values, the
 //    counter-correction pieces (in-chunk correction total, sparse reset
 //    table, updateCorrection operand), and the interpolation-search slope.
 //    Query-independent, amortized across queries.
@@ -51,7 +51,8 @@ struct ChunkSum {            // 192 B per chunk, in a device-resident array
   int32_t changes_in;        // interior value changes (NaN-aware)
   float   inv_slope;         // (n-1)/(ts_last-ts0); 0 when degenerate
   uint8_t v0_nan, dropped, dense, ndrops;
-  int32_t _pad[3];
+  int32_t resets_in;         // interior resets: x < px, both non-NaN
+  int32_t _pad[2];
 };
 static_assert(sizeof(ChunkSum) == 192, "ChunkSum layout");
 
@@ -88,7 +89,7 @@ void summary_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
     s.vmin = NAN; s.vmax = NAN; s.first_val = NAN; s.last_val = NAN;
     if (n > 0) {
       double sum = 0, sq = 0, mn = NAN, mx = NAN;
-      int cnt = 0, changes = 0;
+      int cnt = 0, changes = 0, resets = 0;
       double carry_raw = NAN;                 // previous row's raw value
       double corr_carry = 0;                  // drop-scan carries
       double corr_x = -1.7976931348623157e308;
@@ -113,6 +114,9 @@ void summary_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
         if (lane == 0) px = carry_raw;
         changes += (i > 0 && live && !isnan(raw) && !isnan(px) && raw != px)
                        ? 1 : 0;
+        // interior resets (ResetsFunction, RangeInstantFunctions.scala:355-365)
+        resets += (i > 0 && live && !isnan(raw) && !isnan(px) && raw < px)
+                      ? 1 : 0;
         carry_raw = __shfl(raw, 63);
         // counter-reset scan (NaN→0; CorrectingDoubleVectorReader :325-342);
         // table slots published through LDS so lane 0 can emit them
@@ -143,6 +147,7 @@ void summary_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
         sq += __shfl_down(sq, off);
         cnt += __shfl_down(cnt, off);
         changes += __shfl_down(changes, off);
+        resets += __shfl_down(resets, off);
         double o = __shfl_down(mn, off);
         if (!isnan(o) && (isnan(mn) || o < mn)) mn = o;
         o = __shfl_down(mx, off);
@@ -156,6 +161,7 @@ void summary_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
       s.ts0 = ts[0];
       s.ts_last = ts[n - 1];
       s.sum = sum; s.sqsum = sq; s.cnt = cnt; s.changes_in = changes;
+      s.resets_in = resets;
       s.vmin = mn; s.vmax = mx;
       s.first_val = val[0];
       s.last_val = val[n - 1];
@@ -311,7 +317,7 @@ void stream_walk_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
         double sum = NAN, sqsum = NAN, mm = NAN;
         double changes = NAN, prev = NAN;
         double last_val = NAN, last_sample = NAN;
-        int64_t last_ts = -1;
+        int64_t last_ts = -1, prev_ts = -1;
         int icount = 0;
         for (int c = 0; c < nchunks; c++) {
           const int64_t cend = dir.end_time[first + c];
@@ -407,25 +413,42 @@ void stream_walk_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
               if (!isnan(csq) && isnan(sqsum)) sqsum = 0;
               sqsum += csq;
               icount += cc;
-            } else {  // FN_CHANGES
+            } else if constexpr (FUNC == FN_IRATE || FUNC == FN_IDELTA) {
+              // the window's last two rows: a range of >= 2 rows supplies
+              // both, a 1-row range shifts last -> prev (the previous sample
+              // is then the last row of the preceding visited range)
+              const int rn = endRow - startRow + 1;
+              if (rn >= 2) {
+                prev_ts = d_lv_at(&tv, endRow - 1);
+                prev = d_dv_at(&vv, endRow - 1);
+              } else {
+                prev_ts = last_ts; prev = last_val;
+              }
+              last_ts = (endRow == n - 1) ? cs.ts_last : d_lv_at(&tv, endRow);
+              last_val = (endRow == n - 1) ? cs.last_val : d_dv_at(&vv, endRow);
+              icount += rn;
+            } else {  // FN_CHANGES / FN_RESETS: x != p / x < p, NaN never counts
+              constexpr bool IS_RESETS = (FUNC == FN_RESETS);
               if (isnan(changes)) changes = 0;
               double first_raw, last_raw;
               double ch;
               if (full) {
-                ch = (double)cs.changes_in;
+                ch = (double)(IS_RESETS ? cs.resets_in : cs.changes_in);
                 first_raw = cs.first_val; last_raw = cs.last_val;
               } else {
                 ch = 0;
                 double p = NAN;
                 for (int i = startRow; i <= endRow; i++) {
                   double x = d_dv_at(&vv, i);
-                  if (i > startRow && !isnan(x) && !isnan(p) && x != p) ch += 1;
+                  if (i > startRow && !isnan(x) && !isnan(p) &&
+                      (IS_RESETS ? x < p : x != p)) ch += 1;
                   p = x;
                 }
                 first_raw = d_dv_at(&vv, startRow);
                 last_raw = p;
               }
-              if (!isnan(first_raw) && !isnan(prev) && first_raw != prev)
+              if (!isnan(first_raw) && !isnan(prev) &&
+                  (IS_RESETS ? first_raw < prev : first_raw != prev))
                 ch += 1;                      // cross-chunk boundary pair
               changes += ch;
               prev = last_raw;
@@ -451,7 +474,23 @@ void stream_walk_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
               result = (FUNC == FN_STDDEV) ? sqrt(r) : r;
             } else result = isnan(sum) ? sum : 0;
           } break;
-          case FN_CHANGES: result = changes; break;
+          case FN_CHANGES: case FN_RESETS: result = changes; break;
+          case FN_IDELTA:
+            // instantValue(isRate=false), RangeInstantFunctions.scala:68-95
+            if (icount >= 2) result = last_val - prev;
+            break;
+          case FN_IRATE:
+            // instantValue(isRate=true) over counter-corrected rows with the
+            // common correction cancelled: NaN -> 0, a drop
+            // yields last; one divide, then one multiply
+            if (icount >= 2) {
+              const double l = isnan(last_val) ? 0 : last_val;
+              const double p = isnan(prev) ? 0 : prev;
+              const double d = (l < p) ? l : l - p;
+              const double dt = (double)(last_ts - prev_ts);
+              result = (dt == 0) ? NAN : d / dt * 1000.0;
+            }
+            break;
           case FN_LAST: case FN_PRESENT: case FN_TIMESTAMP:
             result = last_val; break;
           case FN_ZSCORE: {
@@ -497,6 +536,7 @@ bool fdb_stream_walk_supported(int func_id) {
     case FN_MIN: case FN_MAX: case FN_STDDEV: case FN_STDVAR:
     case FN_CHANGES: case FN_LAST: case FN_PRESENT: case FN_TIMESTAMP:
     case FN_ZSCORE:
+    case FN_IRATE: case FN_IDELTA: case FN_RESETS:
       return true;
     default:
       return false;
@@ -524,6 +564,7 @@ int32_t fdb_launch_stream_walk(hipStream_t stream, const uint8_t* blob,
     SCASE(FN_MIN); SCASE(FN_MAX); SCASE(FN_STDDEV); SCASE(FN_STDVAR);
     SCASE(FN_CHANGES); SCASE(FN_LAST); SCASE(FN_PRESENT); SCASE(FN_TIMESTAMP);
     SCASE(FN_ZSCORE);
+    SCASE(FN_IRATE); SCASE(FN_IDELTA); SCASE(FN_RESETS);
     default:
       fdb_set_error("stream walk: unsupported func_id %d", func_id);
       return FDB_ERR_BADARG;

@@ -11,6 +11,8 @@
 //   QuantileOverTimeChunkedFunctionD    AggrOverTimeFunctions.scala:1272-1299
 //   MedianAbsoluteDeviationOverTime...  AggrOverTimeFunctions.scala:1302-1330
 //   PredictLinearChunkedFunctionD       AggrOverTimeFunctions.scala:1507-1554
+//   DerivFunction (FN 24; regression slope, x from the window's first row,
+//   NaNs included, no buffer)           RangeInstantFunctions.scala:10-18,45-66
 // Works on any dataset shape (no chunk summaries needed — search slopes are
 // derived from each chunk's first/last timestamps on the fly).
 // Capacity: <= WS_MAX_SAMPLES non-NaN samples per window (loud error beyond,
@@ -73,6 +75,7 @@ void window_sample_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
     bool touched = false, over = false;
     double plX = NAN, plY = NAN, plXY = NAN, plX2 = NAN;   // predict_linear
     int plN = 0;
+    int64_t drv_t0 = 0;                     // deriv: the window's first ts
     double hwS = NAN, hwB = NAN, hwNext = NAN, hwRes = NAN; // holt_winters
     const bool collect =
         (FUNC != FN_QUANTILE) || (param >= 0 && param <= 1);
@@ -114,6 +117,29 @@ void window_sample_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
             else { plY += sy; plX += sx; plXY += sxy; plX2 += sx2; }
             plN += cnt;
           }
+        } else if constexpr (FUNC == FN_DERIV) {
+          // DerivFunction (RangeInstantFunctions.scala:10-18,45-66): the
+          // same regression sums with x measured from the window's FIRST
+          // row, and NaN samples included (the sliding path feeds them in,
+          // so any NaN in the window gives NaN and n counts every row). No
+          // sample buffer, so no cap on the window's rows.
+          if (plN == 0)
+            drv_t0 = (startRow == 0) ? ts0 : d_lv_at(&tv, startRow);
+          double sx = 0, sy = 0, sxy = 0, sx2 = 0;
+          for (int i = startRow + lane; i <= endRow; i += 64) {
+            double y = d_dv_at(&vv, i);
+            double x = (double)(d_lv_at(&tv, i) - drv_t0) / 1000.0;
+            sx += x; sy += y; sxy += x * y; sx2 += x * x;
+          }
+          for (int off = 32; off > 0; off >>= 1) {
+            sx += __shfl_down(sx, off); sy += __shfl_down(sy, off);
+            sxy += __shfl_down(sxy, off); sx2 += __shfl_down(sx2, off);
+          }
+          sx = __shfl(sx, 0); sy = __shfl(sy, 0);
+          sxy = __shfl(sxy, 0); sx2 = __shfl(sx2, 0);
+          if (plN == 0) { plY = sy; plX = sx; plXY = sxy; plX2 = sx2; }
+          else { plY += sy; plX += sx; plXY += sxy; plX2 += sx2; }
+          plN += endRow - startRow + 1;
         } else if constexpr (FUNC == FN_HOLT_WINTERS) {
           // HoltWintersChunkedFunctionD (AggrOverTimeFunctions.scala:
           // 1379-1452), the oracle's exact operation sequence serial on
@@ -192,6 +218,12 @@ void window_sample_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
         double intercept = plY / plN - slope * plX / plN;
         result = slope * param + intercept;
       }
+    } else if constexpr (FUNC == FN_DERIV) {
+      if (plN >= 2) {                       // linearRegression's slope
+        double covXY = plXY - plX * plY / plN;
+        double varX = plX2 - plX * plX / plN;
+        result = covXY / varX;
+      }
     } else {
       if (FUNC == FN_QUANTILE && touched && param < 0) result = -INFINITY;
       else if (FUNC == FN_QUANTILE && touched && param > 1) result = INFINITY;
@@ -263,7 +295,8 @@ void window_sample_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
 
 bool fdb_window_sample_supported(int func_id) {
   return func_id == FN_QUANTILE || func_id == FN_MAD ||
-         func_id == FN_PREDICT_LINEAR || func_id == FN_HOLT_WINTERS;
+         func_id == FN_PREDICT_LINEAR || func_id == FN_HOLT_WINTERS ||
+         func_id == FN_DERIV;
 }
 
 int32_t fdb_launch_window_sample(hipStream_t stream, const uint8_t* blob,
@@ -294,6 +327,11 @@ int32_t fdb_launch_window_sample(hipStream_t stream, const uint8_t* blob,
       break;
     case FN_HOLT_WINTERS:
       hipLaunchKernelGGL((window_sample_kernel<FN_HOLT_WINTERS>),
+                         dim3((uint32_t)grid), dim3(WS_WAVES * 64), 0, stream,
+                         WARGS);
+      break;
+    case FN_DERIV:
+      hipLaunchKernelGGL((window_sample_kernel<FN_DERIV>),
                          dim3((uint32_t)grid), dim3(WS_WAVES * 64), 0, stream,
                          WARGS);
       break;

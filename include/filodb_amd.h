@@ -183,6 +183,23 @@ int32_t fdb_nibblepack_pack_doubles(const double* in, int32_t n, uint8_t* out, i
 #define FDB_FN_ZSCORE          15   /* ZScoreChunkedFunctionD
                                        (AggrOverTimeFunctions.scala:1592-1603):
                                        (lastSample - mean) / stddev over the window */
+/* Instant range functions (RangeFunction.scala:489-494, served by the sliding
+ * iterator in the reference; RangeInstantFunctions.scala). Windows are the
+ * same inclusive [wEnd - window, wEnd]; param/param2 are ignored. */
+#define FDB_FN_IRATE           21   /* IRateFunction (RangeInstantFunctions.scala:168-183,
+                                       instantValue :68-95 over counter-corrected rows):
+                                       per-second rate of the window's last two samples;
+                                       NaN -> 0, a drop yields the last value; NaN with
+                                       fewer than two samples */
+#define FDB_FN_IDELTA          22   /* IDeltaFunction (RangeInstantFunctions.scala:202-217):
+                                       raw difference of the window's last two samples */
+#define FDB_FN_RESETS          23   /* ResetsFunction (RangeInstantFunctions.scala:352-384):
+                                       adjacent non-NaN pairs with v[i] < v[i-1];
+                                       NaN for an empty window */
+#define FDB_FN_DERIV           24   /* DerivFunction (RangeInstantFunctions.scala:10-18,
+                                       linearRegression :45-66): least-squares slope per
+                                       second, x from the window's first sample; NaN
+                                       samples are not skipped */
 
 /* Cross-series aggregation: RowAggregator implementations
  * (query/.../exec/aggregator/RowAggregator.scala:28-150). */
