@@ -1,6 +1,9 @@
-// Cross-series quantile (t-digest) and count_values aggregators on the GPU.
+// Presenter kernels: everything that runs after a scan, over the per-series
+// [S×W] grid or the aggregated [G×W] grids (group reduce, top/bottom-k, the
+// aggregate presentation fixup, histogram quantile, avg division), and the
+// cross-series quantile (t-digest) and count_values aggregators.
 //
-// Both run as presenters over the per-series [S×W] grid the scan writes
+// The last two run as presenters over the per-series [S×W] grid the scan writes
 // (the two-phase reduce of DESIGN.md §4): one THREAD per (group, window)
 // cell walks its group's members in ascending series order — the exact
 // insertion order of the oracle's fold, and the reference's fastReduce
@@ -14,17 +17,11 @@
 //                 per cell; > limit distinct values is an error — the
 //                 reference throws at 1000)
 
-#include <hip/hip_runtime.h>
-#include <cstdint>
 #include <cstring>
 #include <cmath>
 
-#include "chunk_format.h"
-#include "scan_common.h"
+#include "engine_internal.h"
 #include "tdigest_impl.h"
-#include "../../include/filodb_amd.h"
-
-void fdb_set_error(const char* fmt, ...);   // chunk_builder.cpp
 
 __global__ __launch_bounds__(64)
 void quantile_cell_kernel(const double* __restrict__ grid,
@@ -79,6 +76,210 @@ void count_values_kernel(const double* __restrict__ grid,
   }
 }
 
+// cross-series group reduction from a per-series [S×W] grid. Replaces the
+// contended-atomic accumulation path: the scan writes plain per-series window
+// results (identical to AGG_NONE) and this kernel folds each group's
+// contiguous members from the group-sorted index — one coalesced read of the
+// grid instead of 2-3 f64 RMWs per (series, window) on a hot [G×W] grid.
+// Semantics: RangeVectorAggregator.fastReduce (AggrOverRangeVectors.scala:
+// 320-377) with the RowAggregator map/reduce rules (NaN rows skipped; MIN/MAX
+// stay NaN until a value arrives). Raw sums+counts out — agg_present_kernel
+// applies the presentation step, as the atomic path did.
+__global__ void group_reduce_kernel(const double* __restrict__ grid,
+                                    const int32_t* __restrict__ sbg,
+                                    const int32_t* __restrict__ goff,
+                                    int ng, int nw, int agg_id,
+                                    double* __restrict__ out,
+                                    double* __restrict__ cnt,
+                                    double* __restrict__ sq) {
+  size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (size_t)ng * nw) return;
+  int g = (int)(idx / nw), w = (int)(idx % nw);
+  // consecutive threads share g and walk consecutive w, so each member's row
+  // grid[s*nw + w..] is read coalesced across the wave
+  const int i0 = goff[g], i1 = goff[g + 1];
+  if (agg_id == AGG_MIN || agg_id == AGG_MAX) {
+    const bool is_min = agg_id == AGG_MIN;
+    double acc = NAN, c = 0.0;
+    for (int i = i0; i < i1; i++) {
+      double x = grid[(size_t)sbg[i] * nw + w];
+      if (isnan(x)) continue;
+      c += 1.0;
+      acc = isnan(acc) || (is_min ? x < acc : x > acc) ? x : acc;
+    }
+    out[idx] = acc;
+    cnt[idx] = c;
+    if (sq) sq[idx] = 0.0;
+    return;
+  }
+  // sum-shaped reductions: 4 independent accumulator chains keep 4 loads in
+  // flight (a single chain leaves the loop latency-bound far below the HBM
+  // rate). Reordering the member sum is fine: the atomic path this replaced
+  // already accumulated in nondeterministic order.
+  double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+  double c0 = 0, c1 = 0, q0 = 0, q1 = 0;
+  int i = i0;
+  for (; i + 3 < i1; i += 4) {
+    double x0 = grid[(size_t)sbg[i] * nw + w];
+    double x1 = grid[(size_t)sbg[i + 1] * nw + w];
+    double x2 = grid[(size_t)sbg[i + 2] * nw + w];
+    double x3 = grid[(size_t)sbg[i + 3] * nw + w];
+    bool n0 = !isnan(x0), n1 = !isnan(x1), n2 = !isnan(x2), n3 = !isnan(x3);
+    a0 += n0 ? x0 : 0.0; a1 += n1 ? x1 : 0.0;
+    a2 += n2 ? x2 : 0.0; a3 += n3 ? x3 : 0.0;
+    c0 += (double)n0 + (double)n2; c1 += (double)n1 + (double)n3;
+    q0 += n0 ? x0 * x0 : 0.0; q1 += n1 ? x1 * x1 : 0.0;
+    q0 += n2 ? x2 * x2 : 0.0; q1 += n3 ? x3 * x3 : 0.0;
+  }
+  for (; i < i1; i++) {
+    double x = grid[(size_t)sbg[i] * nw + w];
+    if (isnan(x)) continue;
+    a0 += x; c0 += 1.0; q0 += x * x;
+  }
+  double c = c0 + c1;
+  out[idx] = (agg_id == AGG_COUNT || agg_id == AGG_GROUP)
+                 ? c : (a0 + a1) + (a2 + a3);
+  cnt[idx] = c;
+  if (sq) sq[idx] = q0 + q1;
+}
+
+// top/bottom-k presenter (TopBottomKRowAggregator.scala:29-100): one thread
+// per (group, window) walks its group's series in ascending id order over the
+// [S×W] grid, maintaining a sorted k-list — identical insertion order to the
+// oracle's fold, so results (including ties) match exactly.
+__global__ void topk_kernel(const double* __restrict__ grid,
+                            const int32_t* __restrict__ sbg,
+                            const int32_t* __restrict__ goff,
+                            int ng, int nw, int k, int top,
+                            double* __restrict__ out, double* __restrict__ ids) {
+  size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (size_t)ng * nw) return;
+  int g = (int)(idx / nw), w = (int)(idx % nw);
+  double best[16], bid[16];
+  for (int j = 0; j < 16; j++) { best[j] = NAN; bid[j] = -1; }
+  for (int i = goff[g]; i < goff[g + 1]; i++) {
+    int s = sbg[i];
+    double x = grid[(size_t)s * nw + w];
+    if (isnan(x)) continue;
+    int pos = -1;
+    for (int j = 0; j < k; j++)
+      if (isnan(best[j]) || (top ? x > best[j] : x < best[j])) { pos = j; break; }
+    if (pos >= 0) {
+      for (int j = k - 1; j > pos; j--) { best[j] = best[j - 1]; bid[j] = bid[j - 1]; }
+      best[pos] = x; bid[pos] = (double)s;
+    }
+  }
+  for (int j = 0; j < k; j++) {
+    out[idx * k + j] = best[j];
+    if (ids) ids[idx * k + j] = bid[j];
+  }
+}
+
+// presentation fixup for aggregated grids (NaN where no contributions; mean for avg)
+__global__ void agg_present_kernel(double* out, const double* cnt, const double* sq,
+                                   size_t n, int agg_id, int partial) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (partial) return;                      // partial mode: leave raw sums + counts
+  if (cnt[i] <= 0) { out[i] = NAN; return; }
+  if (agg_id == AGG_GROUP) out[i] = 1.0;   // GroupRowAggregator.scala:12-31
+  else if (agg_id == AGG_AVG) out[i] = out[i] / cnt[i];
+  else if (agg_id == AGG_STDDEV || agg_id == AGG_STDVAR) {
+    double mean = out[i] / cnt[i];
+    double var = sq[i] / cnt[i] - mean * mean;   // StddevRowAggregator.scala:49-52
+    out[i] = agg_id == AGG_STDDEV ? sqrt(var) : var;
+  }
+}
+
+// quantile present step (Histogram.quantile, Histogram.scala:63-108; geometric)
+__global__ void hist_quantile_kernel(const double* __restrict__ sums,
+                                     const double* __restrict__ cnt,
+                                     double* __restrict__ out,
+                                     size_t cells, int nb, double q,
+                                     double first, double mult) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= cells) return;
+  if (!(cnt[i] > 0)) { out[i] = NAN; return; }
+  const double* v = sums + i * nb;
+  double top = v[nb - 1];
+  if (q < 0) { out[i] = -INFINITY; return; }
+  if (q > 1) { out[i] = INFINITY; return; }
+  if (nb < 2 || !(top > 0)) { out[i] = NAN; return; }
+  double rank = q * top;
+  int bucket = 0;
+  while (v[bucket] < rank) bucket++;
+  double bucketStart = bucket == 0 ? 0 : first * pow(mult, bucket - 1);
+  double bucketEnd = first * pow(mult, bucket);
+  if (bucket == nb - 1 && isinf(bucketEnd)) { out[i] = first * pow(mult, nb - 2); return; }
+  if (bucket == 0 && first <= 0) { out[i] = first; return; }
+  double count = bucket == 0 ? v[0] : v[bucket] - v[bucket - 1];
+  rank -= bucket == 0 ? 0 : v[bucket - 1];
+  out[i] = bucketStart + (bucketEnd - bucketStart) * (rank / count);
+}
+
+__global__ void avg_div_kernel(double* __restrict__ out,
+                               const double* __restrict__ a,
+                               const double* __restrict__ b, size_t n) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = a[i] / b[i];
+}
+
+// ---------------------------------------------------------------------------
+// host-side launchers (prototypes in engine_internal.h)
+// ---------------------------------------------------------------------------
+static int32_t launched(const char* kernel) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    fdb_set_error("%s launch failed: %s", kernel, hipGetErrorString(e));
+    return FDB_ERR;
+  }
+  return FDB_OK;
+}
+
+// one thread per element, 256-thread blocks
+static dim3 blocks256(size_t n) { return dim3((uint32_t)((n + 255) / 256)); }
+
+int32_t fdb_launch_group_reduce(hipStream_t stream, const double* grid,
+                                const int32_t* sbg, const int32_t* goff,
+                                int ng, int nw, int agg_id,
+                                double* out, double* cnt, double* sq) {
+  hipLaunchKernelGGL(group_reduce_kernel, blocks256((size_t)ng * nw), dim3(256),
+                     0, stream, grid, sbg, goff, ng, nw, agg_id, out, cnt, sq);
+  return launched("group_reduce_kernel");
+}
+
+int32_t fdb_launch_topk(hipStream_t stream, const double* grid,
+                        const int32_t* sbg, const int32_t* goff,
+                        int ng, int nw, int k, int top,
+                        double* out, double* ids) {
+  hipLaunchKernelGGL(topk_kernel, blocks256((size_t)ng * nw), dim3(256), 0,
+                     stream, grid, sbg, goff, ng, nw, k, top, out, ids);
+  return launched("topk_kernel");
+}
+
+int32_t fdb_launch_agg_present(hipStream_t stream, double* out,
+                               const double* cnt, const double* sq,
+                               size_t n, int agg_id, int partial) {
+  hipLaunchKernelGGL(agg_present_kernel, blocks256(n), dim3(256), 0, stream,
+                     out, cnt, sq, n, agg_id, partial);
+  return launched("agg_present_kernel");
+}
+
+int32_t fdb_launch_hist_quantile(hipStream_t stream, const double* sums,
+                                 const double* cnt, double* out, size_t cells,
+                                 int nb, double q, double first, double mult) {
+  hipLaunchKernelGGL(hist_quantile_kernel, blocks256(cells), dim3(256), 0,
+                     stream, sums, cnt, out, cells, nb, q, first, mult);
+  return launched("hist_quantile_kernel");
+}
+
+int32_t fdb_launch_avg_div(hipStream_t stream, double* out, const double* a,
+                           const double* b, size_t n) {
+  hipLaunchKernelGGL(avg_div_kernel, blocks256(n), dim3(256), 0, stream,
+                     out, a, b, n);
+  return launched("avg_div_kernel");
+}
+
 int32_t fdb_launch_quantile_cells(hipStream_t stream, const double* grid,
                                   const int32_t* sbg, const int32_t* goff,
                                   int ng, int nw, double q, double* out) {
@@ -86,12 +287,7 @@ int32_t fdb_launch_quantile_cells(hipStream_t stream, const double* grid,
   hipLaunchKernelGGL(quantile_cell_kernel,
                      dim3((uint32_t)((cells + 63) / 64)), dim3(64), 0, stream,
                      grid, sbg, goff, ng, nw, q, out);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    fdb_set_error("quantile_cell_kernel launch failed: %s", hipGetErrorString(e));
-    return FDB_ERR;
-  }
-  return FDB_OK;
+  return launched("quantile_cell_kernel");
 }
 
 int32_t fdb_launch_count_values(hipStream_t stream, const double* grid,
@@ -108,10 +304,5 @@ int32_t fdb_launch_count_values(hipStream_t stream, const double* grid,
                      dim3((uint32_t)((cells + 63) / 64)), dim3(64), 0, stream,
                      grid, sbg, goff, ng, nw, k_cap, out_vals, out_cnts,
                      out_n, overflow);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    fdb_set_error("count_values_kernel launch failed: %s", hipGetErrorString(e));
-    return FDB_ERR;
-  }
-  return FDB_OK;
+  return launched("count_values_kernel");
 }

@@ -39,10 +39,7 @@
 #include <vector>
 #include <unordered_map>
 
-#include "chunk_format.h"
-#include "../../include/filodb_amd.h"
-
-void fdb_set_error(const char* fmt, ...);
+#include "engine_internal.h"
 
 // engine-internal store access (chunk_builder.cpp)
 extern "C" int32_t fdb_store_add_series(fdb_store_t* s, int32_t group_id, int32_t kind);

@@ -23,8 +23,7 @@
 #include <string>
 #include <limits>
 
-#include "chunk_format.h"
-#include "../../include/filodb_amd.h"
+#include "engine_internal.h"
 
 // ---------------------------------------------------------------------------
 // error handling

@@ -71,7 +71,10 @@
 
 /* approx-const acceptance band for timestamp DDV (DeltaDeltaVector.scala:46-47) */
 #define FDB_DDV_MAX_APPROX_DELTA  250
-/* default chunk row cap (conf/timeseries-filodb-server: block max-chunk-size) */
+/* default chunk row cap (conf/timeseries-filodb-server: block max-chunk-size;
+ * filodb-defaults.conf:835). The one spelling of the cap: the builder seals at
+ * it, upload refuses longer chunks, and the kernels size their per-chunk LDS
+ * arrays by it. */
 #define FDB_DEFAULT_MAX_ROWS 400
 
 /* Chunk directory entry: the cached ChunkSetInfoReader fields

@@ -21,17 +21,10 @@
 // (tests/test_gpu_encode.py) — the host encoder is itself pinned to the
 // reference by the codec byte-golden tests.
 
-#include <hip/hip_runtime.h>
-#include <cstdint>
 #include <cstring>
 #include <cmath>
 
-#include "chunk_format.h"
-#include "scan_common.h"
-#include "../../include/filodb_amd.h"
-
-void fdb_set_error(const char* fmt, ...);         // chunk_builder.cpp
-hipStream_t fdb_engine_stream(fdb_engine_t* e);   // engine.hip
+#include "engine_internal.h"
 
 
 __device__ __forceinline__ int32_t wave_min_i32(int32_t x) {
@@ -309,45 +302,33 @@ extern "C" int32_t fdb_gpu_encode_chunks(fdb_engine_t* e,
     return FDB_ERR_BADARG;
   }
   hipStream_t stream = fdb_engine_stream(e);
-  int64_t *dts = nullptr, *droffs = nullptr, *dtoff = nullptr, *dvoff = nullptr;
-  double* dvals = nullptr;
-  uint8_t* dout = nullptr;
-  int32_t *dtlen = nullptr, *dvlen = nullptr;
-  int32_t rc = FDB_ERR;
-  if (hipMalloc(&dts, (size_t)nrows * 8) != hipSuccess) goto done;
-  if (hipMalloc(&dvals, (size_t)nrows * 8) != hipSuccess) goto done;
-  if (hipMalloc(&droffs, ((size_t)num_chunks + 1) * 8) != hipSuccess) goto done;
-  if (hipMalloc(&dtoff, (size_t)num_chunks * 8) != hipSuccess) goto done;
-  if (hipMalloc(&dvoff, (size_t)num_chunks * 8) != hipSuccess) goto done;
-  if (hipMalloc(&dtlen, (size_t)num_chunks * 4) != hipSuccess) goto done;
-  if (hipMalloc(&dvlen, (size_t)num_chunks * 4) != hipSuccess) goto done;
-  if (hipMalloc(&dout, (size_t)need) != hipSuccess) goto done;
-  if (hipMemset(dout, 0, (size_t)need) != hipSuccess) goto done;
-  if (hipMemcpy(dts, ts, (size_t)nrows * 8, hipMemcpyHostToDevice) != hipSuccess) goto done;
-  if (hipMemcpy(dvals, vals, (size_t)nrows * 8, hipMemcpyHostToDevice) != hipSuccess) goto done;
-  if (hipMemcpy(droffs, row_offs, ((size_t)num_chunks + 1) * 8, hipMemcpyHostToDevice) != hipSuccess) goto done;
-  if (hipMemcpy(dtoff, out_ts_off, (size_t)num_chunks * 8, hipMemcpyHostToDevice) != hipSuccess) goto done;
-  if (hipMemcpy(dvoff, out_val_off, (size_t)num_chunks * 8, hipMemcpyHostToDevice) != hipSuccess) goto done;
-  {
-    int grid = (num_chunks + 3) / 4;
-    if (grid > 16384) grid = 16384;
-    hipLaunchKernelGGL(encode_kernel, dim3(grid), dim3(256), 0, stream,
-                       dts, dvals, droffs, num_chunks, col_kind, dout,
-                       dtoff, dvoff, dtlen, dvlen);
-    if (hipGetLastError() != hipSuccess) {
-      fdb_set_error("encode_kernel launch failed");
-      goto done;
-    }
+  DevPtr<int64_t> dts, droffs, dtoff, dvoff;
+  DevBuf dvals;
+  DevPtr<uint8_t> dout;
+  DevPtr<int32_t> dtlen, dvlen;
+  if (!dts.alloc((size_t)nrows * 8) || !dvals.alloc((size_t)nrows * 8) ||
+      !droffs.alloc(((size_t)num_chunks + 1) * 8) ||
+      !dtoff.alloc((size_t)num_chunks * 8) || !dvoff.alloc((size_t)num_chunks * 8) ||
+      !dtlen.alloc((size_t)num_chunks * 4) || !dvlen.alloc((size_t)num_chunks * 4) ||
+      !dout.alloc((size_t)need)) {
+    fdb_set_error("gpu_encode: device allocation failed (out of HBM?)");
+    return FDB_ERR;
   }
-  if (hipStreamSynchronize(stream) != hipSuccess) goto done;
-  if (hipMemcpy(out, dout, (size_t)need, hipMemcpyDeviceToHost) != hipSuccess) goto done;
-  if (hipMemcpy(out_ts_len, dtlen, (size_t)num_chunks * 4, hipMemcpyDeviceToHost) != hipSuccess) goto done;
-  if (hipMemcpy(out_val_len, dvlen, (size_t)num_chunks * 4, hipMemcpyDeviceToHost) != hipSuccess) goto done;
-  rc = FDB_OK;
-done:
-  if (rc != FDB_OK) fdb_set_error("gpu_encode: device error");
-  (void)hipFree(dts); (void)hipFree(dvals); (void)hipFree(droffs);
-  (void)hipFree(dtoff); (void)hipFree(dvoff); (void)hipFree(dtlen);
-  (void)hipFree(dvlen); (void)hipFree(dout);
-  return rc;
+  HIP_CHECK(hipMemset(dout.get(), 0, (size_t)need));
+  HIP_CHECK(hipMemcpy(dts.get(), ts, (size_t)nrows * 8, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(dvals.get(), vals, (size_t)nrows * 8, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(droffs.get(), row_offs, ((size_t)num_chunks + 1) * 8, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(dtoff.get(), out_ts_off, (size_t)num_chunks * 8, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(dvoff.get(), out_val_off, (size_t)num_chunks * 8, hipMemcpyHostToDevice));
+  int grid = (num_chunks + 3) / 4;
+  if (grid > 16384) grid = 16384;
+  hipLaunchKernelGGL(encode_kernel, dim3(grid), dim3(256), 0, stream,
+                     dts.get(), dvals.get(), droffs.get(), num_chunks, col_kind,
+                     dout.get(), dtoff.get(), dvoff.get(), dtlen.get(), dvlen.get());
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(stream));
+  HIP_CHECK(hipMemcpy(out, dout.get(), (size_t)need, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(out_ts_len, dtlen.get(), (size_t)num_chunks * 4, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(out_val_len, dvlen.get(), (size_t)num_chunks * 4, hipMemcpyDeviceToHost));
+  return FDB_OK;
 }

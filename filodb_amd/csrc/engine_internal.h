@@ -1,0 +1,163 @@
+// Declarations shared by the library's translation units and by nothing
+// outside csrc/: the error sink, the engine's stream accessor, the HIP error
+// macros, owning wrappers for device memory and events, and every kernel
+// launcher's prototype. Each defining file includes this header, so a
+// signature that drifts from its declaration is a compile error.
+#ifndef FDB_ENGINE_INTERNAL_H
+#define FDB_ENGINE_INTERNAL_H
+
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+#include "chunk_format.h"
+#include "scan_common.h"
+#include "../../include/filodb_amd.h"
+
+void fdb_set_error(const char* fmt, ...);         // chunk_builder.cpp
+hipStream_t fdb_engine_stream(fdb_engine_t* e);   // engine.hip
+
+#define HIP_CHECK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { \
+  fdb_set_error("%s failed: %s", #expr, hipGetErrorString(_e)); return FDB_ERR; } } while (0)
+#define HIP_CHECK_NULL(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { \
+  fdb_set_error("%s failed: %s", #expr, hipGetErrorString(_e)); return nullptr; } } while (0)
+
+// Device buffer that is freed on every exit of the scope that holds it. It
+// either owns an allocation (alloc) or wraps memory that belongs to someone
+// else (wrap: a caller's device output, or a slice of another buffer) and then
+// frees nothing.
+template <typename T>
+class DevPtr {
+ public:
+  DevPtr() = default;
+  DevPtr(const DevPtr&) = delete;
+  DevPtr& operator=(const DevPtr&) = delete;
+  DevPtr(DevPtr&& o) noexcept : p_(o.p_), owned_(o.owned_) { o.p_ = nullptr; o.owned_ = false; }
+  DevPtr& operator=(DevPtr&& o) noexcept {
+    if (this != &o) { reset(); p_ = o.p_; owned_ = o.owned_; o.p_ = nullptr; o.owned_ = false; }
+    return *this;
+  }
+  ~DevPtr() { reset(); }
+
+  bool alloc(size_t bytes) {
+    reset();
+    if (hipMalloc((void**)&p_, bytes) != hipSuccess) { p_ = nullptr; return false; }
+    owned_ = true;
+    return true;
+  }
+  void wrap(T* p) { reset(); p_ = p; }
+  void reset() {
+    if (owned_) (void)hipFree(p_);
+    p_ = nullptr; owned_ = false;
+  }
+  T* get() const { return p_; }
+  explicit operator bool() const { return p_ != nullptr; }
+
+ private:
+  T* p_ = nullptr;
+  bool owned_ = false;
+};
+using DevBuf = DevPtr<double>;
+
+// hipEvent_t destroyed on scope exit
+class DevEvent {
+ public:
+  DevEvent() = default;
+  DevEvent(const DevEvent&) = delete;
+  DevEvent& operator=(const DevEvent&) = delete;
+  ~DevEvent() { if (ev_) (void)hipEventDestroy(ev_); }
+  hipError_t create() { return hipEventCreate(&ev_); }
+  hipEvent_t get() const { return ev_; }
+
+ private:
+  hipEvent_t ev_ = nullptr;
+};
+
+// range functions the two scan kernels (scan_fast.hip's single-chunk fast path
+// and scan_stream.hip's summary walk) both implement; each launcher rejects
+// anything else itself
+inline bool fdb_scan_supported(int func_id) {
+  switch (func_id) {
+    case FN_RATE: case FN_INCREASE: case FN_DELTA:
+    case FN_SUM: case FN_COUNT: case FN_AVG: case FN_RATE_OVER_DELTA:
+    case FN_MIN: case FN_MAX: case FN_STDDEV: case FN_STDVAR:
+    case FN_CHANGES: case FN_LAST: case FN_PRESENT: case FN_TIMESTAMP:
+    case FN_ZSCORE:
+    case FN_IRATE: case FN_IDELTA: case FN_RESETS:
+      return true;
+    default:
+      return false;
+  }
+}
+
+// scan_fast.hip: single-chunk-per-series fast path
+int32_t fdb_launch_fast_scan(hipStream_t stream, const uint8_t* blob, DirSoA dir,
+                             const int32_t* series_first, const int32_t* series_nchunks,
+                             const int32_t* group_ids, const int32_t* series_by_group,
+                             int num_series,
+                             int64_t qstart, int64_t qstep, int64_t qwindow,
+                             int num_windows, int func_id, int agg_id, int emit_group,
+                             double* out, double* out_cnt, double* out_sq,
+                             int phase_mask);
+
+// scan_stream.hip: unbounded multi-chunk general path (chunk summaries +
+// per-window walk)
+int32_t fdb_launch_summaries(hipStream_t stream, const uint8_t* blob, DirSoA dir,
+                             int64_t num_chunks, void* sums);
+int64_t fdb_chunksum_bytes(int64_t num_chunks);
+int32_t fdb_launch_stream_walk(hipStream_t stream, const uint8_t* blob,
+                               DirSoA dir, const void* sums,
+                               const int32_t* series_first,
+                               const int32_t* series_nchunks, int num_series,
+                               int64_t qstart, int64_t qstep, int64_t qend,
+                               int64_t qwindow, int num_windows, int func_id,
+                               double* out);
+
+// window_sample.hip: per-(series,window) sample-buffer functions (FN 16-18,
+// holt_winters, deriv)
+bool fdb_window_sample_supported(int func_id);
+int32_t fdb_launch_window_sample(hipStream_t stream, const uint8_t* blob,
+                                 DirSoA dir, const int32_t* series_first,
+                                 const int32_t* series_nchunks, int num_series,
+                                 int64_t qstart, int64_t qstep, int64_t qwindow,
+                                 int num_windows, int func_id, double param,
+                                 double param2, double* out, int32_t* overflow);
+
+// hist2.hip: two-cursor histogram walk (unbounded chunks / window ratio)
+int32_t fdb_launch_hist2(hipStream_t stream, const uint8_t* blob, DirSoA dir,
+                         const uint64_t* max_off, const uint64_t* min_off,
+                         const int32_t* series_first,
+                         const int32_t* series_nchunks,
+                         const int32_t* group_ids, int num_series,
+                         int64_t qstart, int64_t qstep, int64_t qwindow,
+                         int num_windows, int nb, int hfunc,
+                         double* out_sums, double* out_cnt,
+                         double* out_max, double* out_min);
+
+// agg_extra.hip: presenters over the per-series [S×W] grid or the [G×W]
+// aggregate grids. sbg/goff are the dataset's group-sorted series index.
+int32_t fdb_launch_group_reduce(hipStream_t stream, const double* grid,
+                                const int32_t* sbg, const int32_t* goff,
+                                int ng, int nw, int agg_id,
+                                double* out, double* cnt, double* sq);
+int32_t fdb_launch_topk(hipStream_t stream, const double* grid,
+                        const int32_t* sbg, const int32_t* goff,
+                        int ng, int nw, int k, int top,
+                        double* out, double* ids);
+int32_t fdb_launch_agg_present(hipStream_t stream, double* out,
+                               const double* cnt, const double* sq,
+                               size_t n, int agg_id, int partial);
+int32_t fdb_launch_hist_quantile(hipStream_t stream, const double* sums,
+                                 const double* cnt, double* out, size_t cells,
+                                 int nb, double q, double first, double mult);
+int32_t fdb_launch_avg_div(hipStream_t stream, double* out, const double* a,
+                           const double* b, size_t n);
+int32_t fdb_launch_quantile_cells(hipStream_t stream, const double* grid,
+                                  const int32_t* sbg, const int32_t* goff,
+                                  int ng, int nw, double q, double* out);
+int32_t fdb_launch_count_values(hipStream_t stream, const double* grid,
+                                const int32_t* sbg, const int32_t* goff,
+                                int ng, int nw, int k_cap,
+                                double* out_vals, double* out_cnts,
+                                int32_t* out_n, int32_t* overflow);
+
+#endif  // FDB_ENGINE_INTERNAL_H

@@ -23,18 +23,11 @@
 // Histogram.compare's top-bucket-down order (Histogram.scala:204-214) —
 // same rules and per-window correction base as v1 (parity-green).
 
-#include <hip/hip_runtime.h>
-#include <cstdint>
 #include <cstring>
 #include <cmath>
 
-#include "chunk_format.h"
-#include "scan_common.h"
-#include "../../include/filodb_amd.h"
+#include "engine_internal.h"
 
-void fdb_set_error(const char* fmt, ...);   // chunk_builder.cpp
-
-#define H2_ROWS 400
 #define H2_WAVES 4
 
 // parse one element's per-lane bucket delta from its NibblePack stream.
@@ -148,8 +141,8 @@ void hist2_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
                   double* __restrict__ out_max,    // [G × W] or null
                   double* __restrict__ out_min,    // [G × W] or null
                   int abl) {   // perf ablation: 1=skip emits, 2=skip decodes
-  __shared__ int64_t tsS_all[H2_WAVES][H2_ROWS];
-  __shared__ int64_t tsE_all[H2_WAVES][H2_ROWS];
+  __shared__ int64_t tsS_all[H2_WAVES][FDB_DEFAULT_MAX_ROWS];
+  __shared__ int64_t tsE_all[H2_WAVES][FDB_DEFAULT_MAX_ROWS];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const int b = lane;
@@ -209,7 +202,7 @@ void hist2_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
       DVec tv;
       d_vec_open_wide(blob + dir.ts_off[first + c], &tv, nullptr);
       cu.nrows = dir.num_rows[first + c];
-      if (cu.nrows > H2_ROWS || cu.nrows > tv.n) cu.nrows = 0;
+      if (cu.nrows > FDB_DEFAULT_MAX_ROWS || cu.nrows > tv.n) cu.nrows = 0;
       d_decode_chunk<false>(tv, cu.nrows, tsbuf, nullptr, lane);
       d_wait_lds();
       __builtin_amdgcn_wave_barrier();

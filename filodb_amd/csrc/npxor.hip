@@ -14,15 +14,9 @@
 // The streams decode bit-exactly against the host/oracle decoder (and
 // roundtrip against packDoubles); 64 doubles retire per prefix pass.
 
-#include <hip/hip_runtime.h>
-#include <cstdint>
 #include <cstring>
 
-#include "chunk_format.h"
-#include "scan_common.h"
-#include "../../include/filodb_amd.h"
-
-void fdb_set_error(const char* fmt, ...);   // chunk_builder.cpp
+#include "engine_internal.h"
 
 __device__ __forceinline__ uint64_t wave_incl_xor(uint64_t x, int lane) {
   for (int off = 1; off < 64; off <<= 1) {
@@ -139,7 +133,6 @@ void xor_unpack_kernel(const uint8_t* __restrict__ blob,
   }
 }
 
-hipStream_t fdb_engine_stream(fdb_engine_t* e);   // engine.hip
 
 // host entry: decodes num_streams packed streams (host memory) on the GPU.
 // offs/counts/out_offs are host arrays; out is a host buffer.
@@ -151,39 +144,30 @@ extern "C" int32_t fdb_gpu_unpack_doubles_xor(fdb_engine_t* e,
                                               int32_t num_streams,
                                               double* out, int64_t out_len) {
   hipStream_t stream = fdb_engine_stream(e);
-  uint8_t* db = nullptr;
-  int64_t *doffs = nullptr, *dooffs = nullptr;
-  int32_t* dcounts = nullptr;
-  double* dout = nullptr;
-  int32_t rc = FDB_ERR;
+  DevPtr<uint8_t> db;
+  DevPtr<int64_t> doffs, dooffs;
+  DevPtr<int32_t> dcounts;
+  DevBuf dout;
   // +256 B tail pad so the wave staging never reads past the blob
-  if (hipMalloc(&db, (size_t)blob_len + 256) != hipSuccess) goto done;
-  if (hipMemset(db + blob_len, 0, 256) != hipSuccess) goto done;
-  if (hipMemcpy(db, blob, (size_t)blob_len, hipMemcpyHostToDevice) != hipSuccess) goto done;
-  if (hipMalloc(&doffs, (size_t)num_streams * 8) != hipSuccess) goto done;
-  if (hipMalloc(&dcounts, (size_t)num_streams * 4) != hipSuccess) goto done;
-  if (hipMalloc(&dooffs, (size_t)num_streams * 8) != hipSuccess) goto done;
-  if (hipMalloc(&dout, (size_t)out_len * 8) != hipSuccess) goto done;
-  if (hipMemcpy(doffs, offs, (size_t)num_streams * 8, hipMemcpyHostToDevice) != hipSuccess) goto done;
-  if (hipMemcpy(dcounts, counts, (size_t)num_streams * 4, hipMemcpyHostToDevice) != hipSuccess) goto done;
-  if (hipMemcpy(dooffs, out_offs, (size_t)num_streams * 8, hipMemcpyHostToDevice) != hipSuccess) goto done;
-  {
-    int grid = (num_streams + 3) / 4;
-    if (grid > 8192) grid = 8192;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(xor_unpack_kernel, dim3(grid), dim3(256), 0, stream,
-                       db, doffs, dcounts, dooffs, num_streams, dout);
-    if (hipGetLastError() != hipSuccess) {
-      fdb_set_error("xor_unpack_kernel launch failed");
-      goto done;
-    }
+  if (!db.alloc((size_t)blob_len + 256) || !doffs.alloc((size_t)num_streams * 8) ||
+      !dcounts.alloc((size_t)num_streams * 4) ||
+      !dooffs.alloc((size_t)num_streams * 8) || !dout.alloc((size_t)out_len * 8)) {
+    fdb_set_error("xor decode: device allocation failed (out of HBM?)");
+    return FDB_ERR;
   }
-  if (hipStreamSynchronize(stream) != hipSuccess) goto done;
-  if (hipMemcpy(out, dout, (size_t)out_len * 8, hipMemcpyDeviceToHost) != hipSuccess) goto done;
-  rc = FDB_OK;
-done:
-  if (rc != FDB_OK && rc == FDB_ERR) fdb_set_error("xor decode device error");
-  (void)hipFree(db); (void)hipFree(doffs); (void)hipFree(dcounts);
-  (void)hipFree(dooffs); (void)hipFree(dout);
-  return rc;
+  HIP_CHECK(hipMemset(db.get() + blob_len, 0, 256));
+  HIP_CHECK(hipMemcpy(db.get(), blob, (size_t)blob_len, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(doffs.get(), offs, (size_t)num_streams * 8, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(dcounts.get(), counts, (size_t)num_streams * 4, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(dooffs.get(), out_offs, (size_t)num_streams * 8, hipMemcpyHostToDevice));
+  int grid = (num_streams + 3) / 4;
+  if (grid > 8192) grid = 8192;
+  if (grid < 1) grid = 1;
+  hipLaunchKernelGGL(xor_unpack_kernel, dim3(grid), dim3(256), 0, stream,
+                     db.get(), doffs.get(), dcounts.get(), dooffs.get(),
+                     num_streams, dout.get());
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(stream));
+  HIP_CHECK(hipMemcpy(out, dout.get(), (size_t)out_len * 8, hipMemcpyDeviceToHost));
+  return FDB_OK;
 }

@@ -48,31 +48,6 @@ struct DVec {           // opened vector header
   uint8_t nbits, sign, dropped;
 };
 
-__device__ inline void d_vec_open(const uint8_t* p, DVec* v) {
-  v->wf = d_u16(p + 4);
-  v->dropped = (d_u16(p + 6) & FDB_DROP_MASK) != 0;
-  if (v->wf == FDB_WF_DDV) {
-    v->init = d_i64(p + FDB_DDV_OFF_INIT);
-    v->slope = d_i32(p + FDB_DDV_OFF_SLOPE);
-    const uint8_t* inner = p + FDB_DDV_OFF_INNER;
-    v->nbits = inner[6] & FDB_NBITS_MASK;
-    v->sign = (inner[6] & FDB_SIGN_MASK) != 0;
-    v->idata = inner + FDB_PRIM_OFF_DATA;
-    int numBytes = (int)d_u32(inner);
-    int bitShift = inner[7] & 0x3f;
-    v->n = ((numBytes - 4) * 8 + (bitShift != 0 ? bitShift - 8 : 0)) / v->nbits;
-  } else if (v->wf == FDB_WF_DDV_CONST) {
-    v->n = d_i32(p + FDB_DDVC_OFF_NELEM);
-    v->init = d_i64(p + FDB_DDVC_OFF_INIT);
-    v->slope = d_i32(p + FDB_DDVC_OFF_SLOPE);
-    v->idata = nullptr; v->nbits = 0; v->sign = 0;
-  } else {
-    v->n = ((int)d_u32(p) - 4) / 8;
-    v->idata = p + FDB_PRIM_OFF_DATA;
-    v->init = 0; v->slope = 0; v->nbits = 64; v->sign = 1;
-  }
-}
-
 __device__ __forceinline__ int64_t d_inner_at(const DVec* v, int i) {
   switch (v->nbits) {
     case 32: return d_i32(v->idata + 4 * (size_t)i);
@@ -104,10 +79,24 @@ __device__ __forceinline__ double d_dv_at(const DVec* v, int i) {
   return (double)d_lv_at(v, i);
 }
 
+// first index in [0,n) with ts[i] >= item; n when none — interpolation guess
+// + exact walk over the encoded vector (DeltaDeltaDataReader.binarySearch
+// semantics for our lower-bound convention)
+__device__ __forceinline__ int d_search_ge(const DVec& tv, int n, int64_t item,
+                                           int64_t ts0, float inv_slope) {
+  if (n <= 0) return 0;
+  int g = (int)((float)(item - ts0) * inv_slope);
+  if (g < 0) g = 0;
+  if (g > n - 1) g = n - 1;
+  while (g > 0 && d_lv_at(&tv, g - 1) >= item) g--;
+  while (g < n && d_lv_at(&tv, g) < item) g++;
+  return g;
+}
+
 // one-load header open: vectors are 64-B aligned in the device blob (padded
 // tail), so a single 32-byte read covers every header field of all three
-// scalar layouts — replaces d_vec_open's ~6 dependent global loads with one
-// round trip. first_val (optional) returns element 0 (ts0 for a timestamp
+// scalar layouts — one round trip instead of the ~6 dependent global loads a
+// field-by-field open costs. first_val (optional) returns element 0 (ts0 for a timestamp
 // vector) parsed from the same 32 bytes.
 __device__ __forceinline__ void d_vec_open_wide(const uint8_t* p, DVec* v,
                                                 int64_t* first_val) {
@@ -413,12 +402,6 @@ __device__ __forceinline__ uint32_t estream_byte(bool staged, uint32_t buf,
     return (d >> ((kk & 3) * 8)) & 0xff;
   }
   return g[k];
-}
-__device__ __forceinline__ uint32_t estream_u16(bool staged, uint32_t buf,
-                                                int shift, const uint8_t* g,
-                                                int k) {
-  return estream_byte(staged, buf, shift, g, k) |
-         (estream_byte(staged, buf, shift, g, k + 1) << 8);
 }
 // wave-UNIFORM byte read from the staged window: kk>>2 is the same for every
 // lane, so v_readlane (scalar result, no LDS pipe) replaces ds_bpermute —

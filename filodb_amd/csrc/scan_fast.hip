@@ -41,19 +41,12 @@
 // materialized (AggrOverRangeVectors.scala:320-377 semantics; raw sums +
 // counts out, agg_present_kernel applies the presentation step).
 
-#include <hip/hip_runtime.h>
-#include <cstdint>
 #include <cstring>
 #include <cmath>
 
-#include "chunk_format.h"
-#include "scan_common.h"
+#include "engine_internal.h"
 #include "window_bounds.h"
-#include "../../include/filodb_amd.h"
 
-void fdb_set_error(const char* fmt, ...);   // chunk_builder.cpp
-
-#define FAST_ROWS 400        // reference chunk row cap (filodb-defaults.conf:835)
 #define FAST_TILE 256        // windows per pass: 4 per lane, unrolled
 #define FAST_WAVES 4
 #define FAST_DROPS 32        // sparse counter-reset table capacity
@@ -77,13 +70,13 @@ template <int FUNC> struct FKind { static constexpr int v =
 
 template <int KIND>
 struct FWs {                        // per-wave LDS workspace
-  int32_t tso[FAST_ROWS + 4];       // ts - ts0 (i32 offsets); the pad keeps
-                                    // tso[startRow] readable at startRow == n
-  double  val[FAST_ROWS];           // raw values, or prefix sums (PFX kinds)
+  int32_t tso[FDB_DEFAULT_MAX_ROWS + 4];   // ts - ts0 (i32 offsets); the pad keeps
+                                           // tso[startRow] readable at startRow == n
+  double  val[FDB_DEFAULT_MAX_ROWS];       // raw values, or prefix sums (PFX kinds)
   uint16_t cnt[(KIND == K_PFX || KIND == K_PFX_SQ || KIND == K_CHANGES)
-                   ? FAST_ROWS : 1];
-  double  sq[KIND == K_PFX_SQ ? FAST_ROWS : 1];
-  double  grp[KIND == K_MINMAX ? (FAST_ROWS + 7) / 8 : 1];
+                   ? FDB_DEFAULT_MAX_ROWS : 1];
+  double  sq[KIND == K_PFX_SQ ? FDB_DEFAULT_MAX_ROWS : 1];
+  double  grp[KIND == K_MINMAX ? (FDB_DEFAULT_MAX_ROWS + 7) / 8 : 1];
   int16_t dpos[KIND == K_RATE ? FAST_DROPS : 1];
   double  dcum[KIND == K_RATE ? FAST_DROPS : 1];
 };
@@ -147,7 +140,7 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
   constexpr int KIND = FKind<FUNC>::v;
   constexpr bool IS_COUNTER = (FUNC == FN_RATE || FUNC == FN_INCREASE);
   __shared__ FWs<KIND> ws_all[FAST_WAVES];
-  __shared__ double inv_tab[NeedsInv<KIND>::v ? FAST_ROWS + 2 : 1];
+  __shared__ double inv_tab[NeedsInv<KIND>::v ? FDB_DEFAULT_MAX_ROWS + 2 : 1];
 
   // readfirstlane pins the wave id (and everything derived from it — series
   // ids, directory offsets, header pointers) as wave-uniform for the
@@ -158,7 +151,7 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
   FWs<KIND>& ws = ws_all[wave];
 
   if (NeedsInv<KIND>::v) {
-    for (int i = threadIdx.x; i < FAST_ROWS + 2; i += FAST_WAVES * 64)
+    for (int i = threadIdx.x; i < FDB_DEFAULT_MAX_ROWS + 2; i += FAST_WAVES * 64)
       inv_tab[i] = 1.0 / (double)i;          // [0] = +inf (never a divisor)
     __syncthreads();
   }
@@ -267,7 +260,7 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
         d_vec_open_wide(blob + voff, &vv, nullptr);
       }
       n = nrows;
-      if (n > FAST_ROWS || n > tv.n) { n = 0; ts0 = 0; }   // guarded at upload
+      if (n > FDB_DEFAULT_MAX_ROWS || n > tv.n) { n = 0; ts0 = 0; }   // guarded at upload
       if (n > 0) {
         d_decode_ts_offsets(tv, n, ts0, ws.tso, lane);
         d_decode_chunk<true>(vv, n, nullptr, ws.val, lane);
@@ -702,20 +695,6 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
 // ---------------------------------------------------------------------------
 // host-side launcher (called from engine.hip's launch dispatch)
 // ---------------------------------------------------------------------------
-bool fdb_fast_scan_supported(int func_id) {
-  switch (func_id) {
-    case FN_RATE: case FN_INCREASE: case FN_DELTA:
-    case FN_SUM: case FN_COUNT: case FN_AVG: case FN_RATE_OVER_DELTA:
-    case FN_MIN: case FN_MAX: case FN_STDDEV: case FN_STDVAR:
-    case FN_CHANGES: case FN_LAST: case FN_PRESENT: case FN_TIMESTAMP:
-    case FN_ZSCORE:
-    case FN_IRATE: case FN_IDELTA: case FN_RESETS:
-      return true;
-    default:
-      return false;
-  }
-}
-
 int32_t fdb_launch_fast_scan(hipStream_t stream, const uint8_t* blob, DirSoA dir,
                              const int32_t* series_first, const int32_t* series_nchunks,
                              const int32_t* group_ids, const int32_t* series_by_group,

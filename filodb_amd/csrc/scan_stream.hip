@@ -24,18 +24,11 @@
 // num_windows. Per-chunk rows stay <= 400 (the reference's own chunk cap,
 // filodb-defaults.conf:835).
 
-#include <hip/hip_runtime.h>
-#include <cstdint>
 #include <cstring>
 #include <cmath>
 
-#include "chunk_format.h"
-#include "scan_common.h"
-#include "../../include/filodb_amd.h"
+#include "engine_internal.h"
 
-void fdb_set_error(const char* fmt, ...);   // chunk_builder.cpp
-
-#define SUM_MAX_ROWS 400
 #define SUM_DROPS 8          // sparse per-chunk counter-reset table capacity
 
 struct ChunkSum {            // 192 B per chunk, in a device-resident array
@@ -62,8 +55,8 @@ static_assert(sizeof(ChunkSum) == 192, "ChunkSum layout");
 __global__ __launch_bounds__(256)
 void summary_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
                     int64_t num_chunks, ChunkSum* __restrict__ out) {
-  __shared__ int64_t ts_all[4][SUM_MAX_ROWS];
-  __shared__ double val_all[4][SUM_MAX_ROWS];
+  __shared__ int64_t ts_all[4][FDB_DEFAULT_MAX_ROWS];
+  __shared__ double val_all[4][FDB_DEFAULT_MAX_ROWS];
   __shared__ int16_t dpos_all[4][SUM_DROPS];
   __shared__ double dcum_all[4][SUM_DROPS];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -76,7 +69,7 @@ void summary_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
     d_vec_open_wide(blob + dir.ts_off[c], &tv, nullptr);
     d_vec_open_wide(blob + dir.val_off[c], &vv, nullptr);
     int n = dir.num_rows[c];
-    if (n > SUM_MAX_ROWS || n > tv.n) n = 0;
+    if (n > FDB_DEFAULT_MAX_ROWS || n > tv.n) n = 0;
     if (n > 0) {
       d_decode_chunk<false>(tv, n, ts, nullptr, lane);
       d_decode_chunk<true>(vv, n, nullptr, val, lane);
@@ -190,20 +183,6 @@ void summary_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
 // ---------------------------------------------------------------------------
 // global-memory row access for the walk kernel's boundary ranges
 // ---------------------------------------------------------------------------
-// first index in [0,n) with ts[i] >= item; n when none — interpolation guess
-// + exact walk over the encoded vector (DeltaDeltaDataReader.binarySearch
-// semantics for our lower-bound convention)
-__device__ __forceinline__ int g_search_ge(const DVec& tv, int n, int64_t item,
-                                           int64_t ts0, float inv_slope) {
-  if (n <= 0) return 0;
-  int g = (int)((float)(item - ts0) * inv_slope);
-  if (g < 0) g = 0;
-  if (g > n - 1) g = n - 1;
-  while (g > 0 && d_lv_at(&tv, g - 1) >= item) g--;
-  while (g < n && d_lv_at(&tv, g) < item) g++;
-  return g;
-}
-
 // in-chunk corrected value at row (CorrectingDoubleVectorReader :305-392):
 // raw NaN→0 plus the correction step function from the sparse table, or a
 // serial recompute when the chunk overflowed the table
@@ -272,9 +251,9 @@ void stream_walk_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
           d_vec_open_wide(blob + dir.ts_off[first + c], &tv, nullptr);
           d_vec_open_wide(blob + dir.val_off[first + c], &vv, nullptr);
           int startRow = (wStart <= cs.ts0) ? 0
-              : g_search_ge(tv, n, wStart, cs.ts0, cs.inv_slope);
+              : d_search_ge(tv, n, wStart, cs.ts0, cs.inv_slope);
           int endRow = (wEnd >= cs.ts_last) ? n - 1
-              : g_search_ge(tv, n, wEnd + 1, cs.ts0, cs.inv_slope) - 1;
+              : d_search_ge(tv, n, wEnd + 1, cs.ts0, cs.inv_slope) - 1;
           if (isCounter && meta_has) {        // detectDropAndCorrection
             double firstv = cs.first_val;
             if (isnan(firstv) || firstv < meta_last) meta_corr += meta_last;
@@ -328,9 +307,9 @@ void stream_walk_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
           d_vec_open_wide(blob + dir.ts_off[first + c], &tv, nullptr);
           d_vec_open_wide(blob + dir.val_off[first + c], &vv, nullptr);
           int startRow = (wStart <= cs.ts0) ? 0
-              : g_search_ge(tv, n, wStart, cs.ts0, cs.inv_slope);
+              : d_search_ge(tv, n, wStart, cs.ts0, cs.inv_slope);
           int endRow = (wEnd >= cs.ts_last) ? n - 1
-              : g_search_ge(tv, n, wEnd + 1, cs.ts0, cs.inv_slope) - 1;
+              : d_search_ge(tv, n, wEnd + 1, cs.ts0, cs.inv_slope) - 1;
 
           if constexpr (FUNC == FN_LAST || FUNC == FN_PRESENT) {
             // LastSampleChunkedFunction.addChunks (RangeFunction.scala:599-614)
@@ -527,20 +506,6 @@ int32_t fdb_launch_summaries(hipStream_t stream, const uint8_t* blob, DirSoA dir
 
 int64_t fdb_chunksum_bytes(int64_t num_chunks) {
   return num_chunks * (int64_t)sizeof(ChunkSum);
-}
-
-bool fdb_stream_walk_supported(int func_id) {
-  switch (func_id) {
-    case FN_RATE: case FN_INCREASE: case FN_DELTA:
-    case FN_SUM: case FN_COUNT: case FN_AVG: case FN_RATE_OVER_DELTA:
-    case FN_MIN: case FN_MAX: case FN_STDDEV: case FN_STDVAR:
-    case FN_CHANGES: case FN_LAST: case FN_PRESENT: case FN_TIMESTAMP:
-    case FN_ZSCORE:
-    case FN_IRATE: case FN_IDELTA: case FN_RESETS:
-      return true;
-    default:
-      return false;
-  }
 }
 
 int32_t fdb_launch_stream_walk(hipStream_t stream, const uint8_t* blob,

@@ -18,32 +18,20 @@
 // Capacity: <= WS_MAX_SAMPLES non-NaN samples per window (loud error beyond,
 // checked host-side as rows-per-window bound cannot exceed total rows).
 
-#include <hip/hip_runtime.h>
-#include <cstdint>
 #include <cstring>
 #include <cmath>
 
-#include "chunk_format.h"
-#include "scan_common.h"
-#include "../../include/filodb_amd.h"
-
-void fdb_set_error(const char* fmt, ...);   // chunk_builder.cpp
+#include "engine_internal.h"
 
 #define WS_MAX_SAMPLES 1024
 #define WS_WAVES 4
 
-// first index in [0,n) with ts[i] >= item (lower bound), by interpolation
-// guess + exact walk over the encoded vector
-__device__ __forceinline__ int ws_search_ge(const DVec& tv, int n, int64_t item,
-                                            int64_t ts0, int64_t tsl) {
-  if (n <= 0) return 0;
-  float inv = (tsl > ts0) ? (float)(n - 1) / (float)(tsl - ts0) : 0.0f;
-  int g = (int)((float)(item - ts0) * inv);
-  if (g < 0) g = 0;
-  if (g > n - 1) g = n - 1;
-  while (g > 0 && d_lv_at(&tv, g - 1) >= item) g--;
-  while (g < n && d_lv_at(&tv, g) < item) g++;
-  return g;
+// d_search_ge's guess slope (rows per ms) from a chunk's first and last
+// timestamps — no chunk summaries here. Evaluated per search, not hoisted: a
+// window usually needs neither search or only one, and holding the slope
+// across both costs registers.
+__device__ __forceinline__ float ws_inv_slope(int n, int64_t ts0, int64_t tsl) {
+  return (tsl > ts0) ? (float)(n - 1) / (float)(tsl - ts0) : 0.0f;
 }
 
 template <int FUNC>
@@ -89,9 +77,10 @@ void window_sample_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
       d_vec_open_wide(blob + dir.val_off[first + c], &vv, nullptr);
       const int n = dir.num_rows[first + c];
       const int64_t tsl = dir.end_time[first + c];
-      int startRow = (wStart <= ts0) ? 0 : ws_search_ge(tv, n, wStart, ts0, tsl);
+      int startRow = (wStart <= ts0) ? 0
+          : d_search_ge(tv, n, wStart, ts0, ws_inv_slope(n, ts0, tsl));
       int endRow = (wEnd >= tsl) ? n - 1
-                                 : ws_search_ge(tv, n, wEnd + 1, ts0, tsl) - 1;
+          : d_search_ge(tv, n, wEnd + 1, ts0, ws_inv_slope(n, ts0, tsl)) - 1;
       if (startRow <= endRow && endRow < n) {
         touched = true;
         if constexpr (FUNC == FN_PREDICT_LINEAR) {
