@@ -27,6 +27,7 @@
 #include <cstdlib>
 
 #include "engine_internal.h"
+#include "fast_desc.h"
 
 // ---------------------------------------------------------------------------
 // host engine
@@ -55,12 +56,16 @@ struct fdb_dataset {
   uint64_t *max_off, *min_off;  // hist companion column offsets (0 = absent)
   int has_mm;               // every hist chunk carries max/min columns
   int has_sc;               // every scalar chunk carries a count column
+  // fast scan decode descriptors, one per series (fast_desc.h), built at
+  // upload when fast_ok; fast_desc_sc describes the count column riding
+  // max_off (has_sc) so avg_sc's second scan takes the same kernel
+  FdbFastDesc *fast_desc, *fast_desc_sc;
 };
 
-// the dataset's chunk directory as the kernels take it; val_override swaps the
-// value column (avg_sc scans the count column riding max_off)
-static DirSoA dir_of(const fdb_dataset_t* d, const uint64_t* val_override = nullptr) {
-  return DirSoA{d->ts_off, val_override ? val_override : d->val_off,
+// the dataset's chunk directory as the kernels take it; count_col swaps the
+// value column for the count column riding max_off (avg_sc)
+static DirSoA dir_of(const fdb_dataset_t* d, bool count_col = false) {
+  return DirSoA{d->ts_off, count_col ? d->max_off : d->val_off,
                 d->start_time, d->end_time, d->num_rows};
 }
 
@@ -113,6 +118,7 @@ extern "C" void fdb_dataset_destroy(fdb_dataset_t* d) {
   (void)hipFree(d->series_by_group); (void)hipFree(d->group_offsets);
   (void)hipFree(d->sums);
   (void)hipFree(d->max_off); (void)hipFree(d->min_off);
+  (void)hipFree(d->fast_desc); (void)hipFree(d->fast_desc_sc);
   delete d;
 }
 
@@ -225,6 +231,34 @@ extern "C" fdb_dataset_t* fdb_dataset_upload(fdb_engine_t* e, const fdb_store_t*
     && upload((void**)&d->group_offsets, goff.data(), goff.size() * 4)
     && upload((void**)&d->max_off, mx_off.data(), nc * 8)
     && upload((void**)&d->min_off, mn_off.data(), nc * 8);
+  // fast scan descriptors: every per-series fact the kernel needs before it
+  // touches the payload, parsed once from the host blob (fast_desc.h). A
+  // vector the record cannot address (not 64-B aligned, or past 2^38 B)
+  // sends the dataset down the general path instead.
+  if (ok && d->fast_ok) {
+    const int32_t ns = view.num_series;
+    for (int col = 0; col < (d->has_sc ? 2 : 1) && d->fast_ok; col++) {
+      const std::vector<uint64_t>& voff = col ? mx_off : val_off;
+      std::vector<FdbFastDesc> desc((size_t)ns);
+      int addressable = 1;
+      #pragma omp parallel for schedule(static) reduction(&:addressable)
+      for (int32_t sid = 0; sid < ns; sid++) {
+        const int32_t c = view.series_first[sid];
+        const bool has = view.series_nchunks[sid] >= 1;
+        if (has && (((ts_off[c] | voff[c]) & 63) != 0 ||
+                    ((ts_off[c] | voff[c]) >> 38) != 0)) {
+          addressable = 0;
+          continue;
+        }
+        fdb_build_fast_desc(view.blob, has ? ts_off[c] : 0, has ? voff[c] : 0,
+                            has ? nr[c] : 0, &desc[(size_t)sid]);
+      }
+      if (!addressable) { d->fast_ok = 0; break; }
+      ok = upload((void**)(col ? &d->fast_desc_sc : &d->fast_desc), desc.data(),
+                  desc.size() * sizeof(FdbFastDesc));
+      if (!ok) break;
+    }
+  }
   if (!ok) {
     fdb_set_error("device upload failed (out of HBM?)");
     fdb_dataset_destroy(d);
@@ -259,12 +293,13 @@ static bool fast_eligible(const fdb_dataset_t* d, const fdb_query_t* q) {
 
 static int32_t launch_scan(fdb_engine_t* e, const fdb_dataset_t* d, const fdb_query_t* q,
                            double* dev_out, double* dev_cnt, double* dev_sq,
-                           const uint64_t* val_override = nullptr) {
-  DirSoA dir = dir_of(d, val_override);
+                           bool count_col = false) {
+  DirSoA dir = dir_of(d, count_col);
   int nw = fdb_num_windows(q);
   if (fast_eligible(d, q) && q->agg_id == AGG_NONE) {
-    return fdb_launch_fast_scan(e->stream, d->blob, dir, d->series_first,
-                                d->series_nchunks, d->group_ids,
+    return fdb_launch_fast_scan(e->stream, d->blob,
+                                count_col ? d->fast_desc_sc : d->fast_desc,
+                                d->group_ids,
                                 d->series_by_group, d->num_series,
                                 q->start, q->step, q->window, nw,
                                 q->func_id, AGG_NONE, /*emit_group=*/0,
@@ -404,7 +439,7 @@ static int32_t run_query(fdb_engine_t* e, const fdb_dataset_t* d, const fdb_quer
       if (dev_sq && !(needs_sq && partial))
         HIP_CHECK(hipMemsetAsync(dev_sq.get(), 0, out_len * 8, e->stream));
       return fdb_launch_fast_scan(
-          e->stream, d->blob, dir_of(d), d->series_first, d->series_nchunks,
+          e->stream, d->blob, d->fast_desc,
           d->group_ids, d->series_by_group, d->num_series,
           q->start, q->step, q->window, nw, q->func_id, q->agg_id,
           /*emit_group=*/1, dev_out.get(), dev_cnt.get(), dev_sq.get(), q->_pad);
@@ -616,7 +651,7 @@ extern "C" int32_t fdb_query_exec_avg_sc(fdb_engine_t* e, const fdb_dataset_t* d
     return alloc_failed("avg_sc");
   int32_t rc = launch_scan(e, d, &q2, dsum.get(), nullptr, nullptr);
   if (rc != FDB_OK) return rc;
-  rc = launch_scan(e, d, &q2, dcnt.get(), nullptr, nullptr, d->max_off);
+  rc = launch_scan(e, d, &q2, dcnt.get(), nullptr, nullptr, /*count_col=*/true);
   if (rc != FDB_OK) return rc;
   rc = fdb_launch_avg_div(e->stream, dout.get(), dsum.get(), dcnt.get(), cells);
   if (rc != FDB_OK) return rc;

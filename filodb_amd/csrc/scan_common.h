@@ -234,8 +234,87 @@ __device__ inline void d_decode_chunk(const DVec& v, int n, int64_t* tout,
   }
 }
 
+// --- four rows per lane: the fast scan's packed-DDV decode (8/16-bit) -------
+// Lane l owns rows 4l..4l+3 of each 256-row pass (400 rows: two passes): one
+// 4- or 8-byte payload load, four results, 128-bit LDS stores. The only guard
+// is the lane's (first row < n), so:
+//  * the output array must be 16-byte aligned and hold 4*ceil(n/4) entries;
+//    rows n..4*ceil(n/4)-1 are written with garbage that nothing interprets
+//    (scan_fast.hip's decode section lists the readers);
+//  * the last active lane reads up to 3 elements, <= 6 bytes, past the
+//    vector's end. Vectors are padded to 64 B inside the blob and the blob
+//    carries a 512-B tail pad, so the bytes exist; they only feed those
+//    garbage rows.
+// Inner data starts at vector + 28: 4-byte aligned, like each lane's slice.
+template <int NBITS>
+__device__ __forceinline__ void d_load_rows4(const uint8_t* idata, int i0,
+                                             bool sign, int32_t d[4]) {
+  static_assert(NBITS == 8 || NBITS == 16, "packed widths with a 4-row slice");
+  if (NBITS == 16) {
+    // unsigned 32-bit byte offsets: a uniform base plus a zero-extended lane
+    // offset addresses through the SGPR-base form, no 64-bit VGPR pair
+    const uint32_t lo = d_u32(idata + 2u * (uint32_t)i0);
+    const uint32_t hi = d_u32(idata + (2u * (uint32_t)i0 + 4u));
+    const int32_t m = sign ? -1 : 0xffff;      // unsigned: drop the extension
+    d[0] = (int32_t)(int16_t)(lo & 0xffff) & m;
+    d[1] = ((int32_t)lo >> 16) & m;
+    d[2] = (int32_t)(int16_t)(hi & 0xffff) & m;
+    d[3] = ((int32_t)hi >> 16) & m;
+  } else {
+    const uint32_t w = d_u32(idata + (uint32_t)i0);
+    const int32_t m = sign ? -1 : 0xff;
+    d[0] = (int32_t)(int8_t)(w & 0xff) & m;
+    d[1] = (int32_t)(int8_t)((w >> 8) & 0xff) & m;
+    d[2] = (int32_t)(int8_t)((w >> 16) & 0xff) & m;
+    d[3] = ((int32_t)w >> 24) & m;
+  }
+}
+
+// values: v[i] = (double)(init + slope*i + inner[i]). exact32 (upload-time
+// flag, fast_desc.h): |init| < 2^52 and off = slope*i + inner[i] fits i32 for
+// every row, so (double)init + (double)off adds two integers whose sum stays
+// below 2^53 — the f64 add is exact and equals the i64 sum's conversion bit
+// for bit, at one v_cvt_f64_i32 and one add per row instead of an i64
+// multiply-add and a four-instruction i64 -> f64 convert.
+template <int NBITS>
+__device__ __forceinline__ void d_decode_val4(const uint8_t* idata, bool sign,
+                                              int64_t init, int32_t slope,
+                                              bool exact32, int n, double* dout,
+                                              int lane) {
+  if (exact32) {
+    const double init_f = (double)init;          // wave-uniform, once per series
+    for (int i0 = 4 * lane; i0 < n; i0 += 256) {
+      int32_t d[4];
+      d_load_rows4<NBITS>(idata, i0, sign, d);
+      const uint32_t b = (uint32_t)slope * (uint32_t)i0;
+      double2 a, c;
+      a.x = init_f + (double)(int32_t)(b + (uint32_t)d[0]);
+      a.y = init_f + (double)(int32_t)(b + (uint32_t)slope + (uint32_t)d[1]);
+      c.x = init_f + (double)(int32_t)(b + 2u * (uint32_t)slope + (uint32_t)d[2]);
+      c.y = init_f + (double)(int32_t)(b + 3u * (uint32_t)slope + (uint32_t)d[3]);
+      *reinterpret_cast<double2*>(dout + i0) = a;
+      *reinterpret_cast<double2*>(dout + i0 + 2) = c;
+    }
+    return;
+  }
+  for (int i0 = 4 * lane; i0 < n; i0 += 256) {
+    int32_t d[4];
+    d_load_rows4<NBITS>(idata, i0, sign, d);
+    const int64_t b = init + (int64_t)slope * i0;
+    double2 a, c;
+    a.x = (double)(b + d[0]);
+    a.y = (double)(b + slope + d[1]);
+    c.x = (double)(b + 2 * (int64_t)slope + d[2]);
+    c.y = (double)(b + 3 * (int64_t)slope + d[3]);
+    *reinterpret_cast<double2*>(dout + i0) = a;
+    *reinterpret_cast<double2*>(dout + i0 + 2) = c;
+  }
+}
+
 // i32-offset decode variant: timestamps relative to the chunk's first ts.
-// Caller guarantees the chunk's time span fits i32 (upload-time check).
+// Caller guarantees the chunk's time span fits i32 (upload-time check). The
+// packed 8/16-bit arms use the four-rows-per-lane layout above: tout must be
+// 16-byte aligned with 4*ceil(n/4) writable entries.
 __device__ inline void d_decode_ts_offsets(const DVec& v, int n, int64_t ts0,
                                            int32_t* tout, int lane) {
   // all arithmetic in i32: the upload guard pins the chunk's span (and so
@@ -253,20 +332,19 @@ __device__ inline void d_decode_ts_offsets(const DVec& v, int n, int64_t ts0,
     return;
   }
   const int32_t base = (int32_t)(v.init - ts0);
-  if (v.nbits == 16) {
+  if (v.nbits == 16 || v.nbits == 8) {
+    const uint32_t sl = (uint32_t)v.slope;
     for (int i0 = 4 * lane; i0 < n; i0 += 256) {
-      uint32_t lo = d_u32(v.idata + 2 * (size_t)i0);
-      uint32_t hi = d_u32(v.idata + 2 * (size_t)i0 + 4);
-      uint64_t w = ((uint64_t)hi << 32) | lo;
-      #pragma unroll
-      for (int k = 0; k < 4; k++) {
-        if (i0 + k < n) {
-          int32_t d = (int32_t)(int16_t)(uint16_t)(w >> (16 * k));
-          if (!v.sign) d &= 0xffff;
-          tout[i0 + k] = (int32_t)((uint32_t)base
-              + (uint32_t)v.slope * (uint32_t)(i0 + k) + (uint32_t)d);
-        }
-      }
+      int32_t d[4];
+      if (v.nbits == 16) d_load_rows4<16>(v.idata, i0, v.sign, d);
+      else               d_load_rows4<8>(v.idata, i0, v.sign, d);
+      const uint32_t b = (uint32_t)base + sl * (uint32_t)i0;
+      int4 r;
+      r.x = (int32_t)(b + (uint32_t)d[0]);
+      r.y = (int32_t)(b + sl + (uint32_t)d[1]);
+      r.z = (int32_t)(b + 2u * sl + (uint32_t)d[2]);
+      r.w = (int32_t)(b + 3u * sl + (uint32_t)d[3]);
+      *reinterpret_cast<int4*>(tout + i0) = r;
     }
     return;
   }

@@ -3,6 +3,18 @@
 // One wave per series: decode the chunk into LDS, build the kind's per-row
 // structures (meta), then evaluate 4 windows per lane.
 //
+//  * per-series bookkeeping comes from a descriptor table built once at
+//    upload (fast_desc.h): sealed chunks never change, so the directory row
+//    and both vector headers are parsed on the host into one 64-byte record
+//    per series — payload offsets, row count (row guards already decided),
+//    wire-format class / nbits / sign, drop bit, ts0, timestamp base and
+//    slope, value init and slope, val_exact32. The kernel loads desc[sid]
+//    through a wave-uniform address and goes straight to the payload: two
+//    dependent memory trips per series instead of the four of
+//    series_first -> directory row -> 32-B headers -> payload
+//  * packed 8/16-bit delta-delta vectors decode four rows per lane (one
+//    payload load, 128-bit LDS stores, no per-row guard; scan_common.h), the
+//    values in exact i32 + f64 arithmetic where val_exact32 holds
 //  * each window's row range [startRow, endRow] is computed directly in the
 //    window phase (window_bounds.h): a linear guess from the series' mean
 //    scrape interval, one secant correction, a four-row LDS probe and an
@@ -41,10 +53,12 @@
 // materialized (AggrOverRangeVectors.scala:320-377 semantics; raw sums +
 // counts out, agg_present_kernel applies the presentation step).
 
+#include <cstddef>
 #include <cstring>
 #include <cmath>
 
 #include "engine_internal.h"
+#include "fast_desc.h"
 #include "window_bounds.h"
 
 #define FAST_TILE 256        // windows per pass: 4 per lane, unrolled
@@ -69,7 +83,9 @@ template <int FUNC> struct FKind { static constexpr int v =
     K_LAST; };   // incl. FN_IRATE / FN_IDELTA: the window's last two raw rows
 
 template <int KIND>
-struct FWs {                        // per-wave LDS workspace
+struct alignas(16) FWs {            // per-wave LDS workspace; tso[] and val[]
+                                    // start 16-B aligned and hold a multiple of
+                                    // four rows (128-bit decode stores)
   int32_t tso[FDB_DEFAULT_MAX_ROWS + 4];   // ts - ts0 (i32 offsets); the pad keeps
                                            // tso[startRow] readable at startRow == n
   double  val[FDB_DEFAULT_MAX_ROWS];       // raw values, or prefix sums (PFX kinds)
@@ -80,6 +96,32 @@ struct FWs {                        // per-wave LDS workspace
   int16_t dpos[KIND == K_RATE ? FAST_DROPS : 1];
   double  dcum[KIND == K_RATE ? FAST_DROPS : 1];
 };
+
+// A descriptor as the kernel holds it: the record's first twelve dwords,
+// loaded as whole dwords through a wave-uniform address (scalar loads have
+// no sub-dword form; a u16/u8 field read would fall back to vector loads and
+// drag everything derived from it into VGPRs). Little-endian field views.
+struct FDesc {
+  uint32_t w[12];
+  __device__ __forceinline__ int n() const { return (int)(w[2] & 0xffff); }
+  __device__ __forceinline__ int ts_cls() const { return (int)((w[2] >> 16) & 0xff); }
+  __device__ __forceinline__ int ts_nbits() const { return (int)(w[2] >> 24); }
+  __device__ __forceinline__ int ts_flags() const { return (int)(w[3] & 0xff); }
+  __device__ __forceinline__ int val_cls() const { return (int)((w[3] >> 8) & 0xff); }
+  __device__ __forceinline__ int val_nbits() const { return (int)((w[3] >> 16) & 0xff); }
+  __device__ __forceinline__ int val_flags() const { return (int)(w[3] >> 24); }
+  __device__ __forceinline__ int64_t ts0() const {
+    return (int64_t)(((uint64_t)w[5] << 32) | w[4]); }
+  __device__ __forceinline__ int32_t ts_base() const { return (int32_t)w[6]; }
+  __device__ __forceinline__ int32_t ts_slope() const { return (int32_t)w[7]; }
+  __device__ __forceinline__ int64_t val_init() const {
+    return (int64_t)(((uint64_t)w[9] << 32) | w[8]); }
+  __device__ __forceinline__ int32_t val_slope() const { return (int32_t)w[10]; }
+};
+static_assert(offsetof(FdbFastDesc, n) == 8 && offsetof(FdbFastDesc, ts_flags) == 12 &&
+              offsetof(FdbFastDesc, ts0) == 16 && offsetof(FdbFastDesc, ts_base) == 24 &&
+              offsetof(FdbFastDesc, val_init) == 32 && offsetof(FdbFastDesc, val_slope) == 40,
+              "FDesc's dword views follow FdbFastDesc's layout");
 
 template <int KIND> struct NeedsInv {   // reciprocal table users (AVG/STDDEV;
   // the rate epilogue keeps the oracle's exact divisions — its threshold
@@ -112,20 +154,18 @@ __device__ __forceinline__ double f_corr_at(const WS& ws, int dcount, bool dense
 // MINW = min waves/SIMD the register allocator must meet. PFX_SQ is
 // LDS-bound at 4 blocks/CU; the group-emit variant carries 12 accumulator
 // registers (4 waves); K_RATE (no reciprocal table, LDS fits 7 blocks/CU) is
-// built at 5 (95 VGPR), 6 (80 VGPR) and 7 (72 VGPR, 20 B scratch with the
-// shared search) — the launcher picks via FDB_RATE_WAVES, default 7 as
-// measured on hardware (profiles/README.md, rounds 3 and 4). The gauge kinds
-// are built at 6: the shared search needs ~10 more VGPRs than the 79 they had,
-// and the bound keeps their sixth wave/SIMD (AVG: 80 VGPR, 12 B scratch). SHARE selects the shared window search
-// (window = 1..64 whole steps; wshare carries that ratio): a template
-// parameter, not a runtime branch — with both searches in one kernel the
-// 79-VGPR gauge kinds grew to 87 and lost their sixth wave/SIMD.
-template <int FUNC, int EMIT, int MINW, bool TIMED = false, bool PF = true,
-          bool SHARE = false>
+// built at 5, 6 and 7 — the launcher picks via FDB_RATE_WAVES, default 7 as
+// measured on hardware (profiles/README.md, rounds 3 and 4); the gauge kinds
+// are built at 6. Since round 5 the bounds no longer bind: with the decoders'
+// lane-scaled blob addresses kept out of the series loop's live set (see the
+// decode section) every plain-grid instantiation sits at 36-53 VGPRs with no
+// scratch (FN_RATE 53, FN_AVG 44), and occupancy is set by LDS alone.
+// SHARE selects the shared window search (window = 1..64 whole steps; wshare
+// carries that ratio): a template parameter, not a runtime branch.
+template <int FUNC, int EMIT, int MINW, bool TIMED = false, bool SHARE = false>
 __global__ __launch_bounds__(FAST_WAVES * 64, MINW)
-void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
-                      const int32_t* __restrict__ series_first,
-                      const int32_t* __restrict__ series_nchunks,
+void fast_scan_kernel(const uint8_t* __restrict__ blob,
+                      const FdbFastDesc* __restrict__ desc,
                       const int32_t* __restrict__ group_ids,
                       const int32_t* __restrict__ sbg,   // EMIT=1: group-sorted order
                       int num_series,
@@ -205,75 +245,73 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
     }
   };
 
-  // two-level software pipeline over the series loop: the dependent chain
-  // series_first[sid] → dir offsets → 32-B vector headers is 3 serial HBM
-  // round trips per series; prefetching each level a stage early hides them
-  // under the previous series' decode/window work (d_wait_lds is lgkm-only,
-  // so prefetch loads stay in flight across the phase fences)
-  int pf_sid = 0, pf_first = 0, pf_nch = 0, pf_nr = 0;
-  uint64_t pf_toff = 0, pf_voff = 0;
-  DVec pf_tv, pf_vv;
-  int64_t pf_ts0 = 0;
-  bool pf_hdr = false;      // pf_tv/pf_vv/pf_ts0 hold the next series' headers
-  if (PF && pos0 < pos1) {
-    pf_sid = (EMIT == 1) ? sbg[pos0] : pos0;
-    pf_first = series_first[pf_sid];
-    pf_nch = series_nchunks[pf_sid];
-    pf_toff = dir.ts_off[pf_first];
-    pf_voff = dir.val_off[pf_first];
-    pf_nr = dir.num_rows[pf_first];
-  }
+  // series bookkeeping: one 64-B descriptor per series (fast_desc.h), parsed
+  // from the vector headers once at upload, fetched here with one scalar load
+  // through a wave-uniform address — the payload is the only dependent trip
+  // behind it. (Requesting desc[next sid] a series early, held in SGPRs, in
+  // VGPRs, or only touched into cache, measured 0.01-0.02 ms SLOWER on
+  // rate_1m than this plain load: at 7 waves/SIMD the second trip is hidden
+  // already. profiles/README.md, round 5.)
+  auto load_desc = [&](int s) {
+    const uint4* p = reinterpret_cast<const uint4*>(desc + s);
+    const uint4 a = p[0], b = p[1], c = p[2];
+    return FDesc{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w}};
+  };
   for (int pos = pos0; pos < pos1; pos += pos_step) {
     if (timing) tt = __builtin_amdgcn_s_memtime();
-    int sid, nch, nrows;
-    uint64_t toff, voff;
-    if (PF) {
-      sid = pf_sid; nch = pf_nch; nrows = pf_nr;
-      toff = pf_toff; voff = pf_voff;
-    } else {
-      sid = (EMIT == 1) ? sbg[pos] : pos;
-      const int first0 = series_first[sid];
-      nch = series_nchunks[sid];
-      toff = dir.ts_off[first0];
-      voff = dir.val_off[first0];
-      nrows = dir.num_rows[first0];
-    }
-    // prefetch stage 1: next series' directory row ids
-    const int npos = pos + pos_step;
-    int nsid = 0, nfirst = 0, nnch = 0;
-    if (PF && npos < pos1) {
-      nsid = (EMIT == 1) ? sbg[npos] : npos;
-      nfirst = series_first[nsid];
-      nnch = series_nchunks[nsid];
-    }
+    const int sid = __builtin_amdgcn_readfirstlane((EMIT == 1) ? sbg[pos] : pos);
+    const FDesc cd = load_desc(sid);
 
     // ---- decode: the single chunk into LDS (i32 ts offsets + f64 values) ---
-    int n = 0;
-    int64_t ts0 = 0;
-    bool dropped = false;
-    if (nch >= 1) {
-      DVec tv, vv;
-      if (pf_hdr) {                    // stage-3 prefetch landed last series
-        tv = pf_tv; vv = pf_vv; ts0 = pf_ts0;
-      } else {
-        d_vec_open_wide(blob + toff, &tv, &ts0);   // one 32-B load each
-        d_vec_open_wide(blob + voff, &vv, nullptr);
+    // n == 0 is an empty series: no chunk, or a guard that upload decided
+    // (rows above the chunk cap, or more rows than the timestamp vector has).
+    // The packed 8/16-bit arms write whole 4-row groups (scan_common.h), so
+    // rows n..4*ceil(n/4)-1 of tso[] and val[] hold garbage. Nothing
+    // interprets them: the meta loops guard i < n, the bound search accepts
+    // rows < n only (window_bounds.h reads past n but never interprets it),
+    // every window row range keeps s <= e < n, and the one tso[s] read at
+    // s == n (shared_bounds) is readable and never used.
+    const int n = cd.n();
+    const int64_t ts0 = cd.ts0();
+    const bool dropped = n > 0 && (cd.val_flags() & FDB_FD_DROPPED) != 0;
+    if (n > 0) {
+      // the decoders see the lane id through an opaque copy made here, per
+      // series: otherwise every arm's lane-scaled blob address (blob + 8*lane,
+      // + 4*lane, ...) is hoisted out of the series loop as a 64-bit VGPR pair
+      // that stays live, or spilled, across the window phase
+      int dl = lane;
+      asm volatile("" : "+v"(dl));
+      const uint8_t* tp = blob + ((size_t)cd.w[0] << 6);
+      const uint8_t* vp = blob + ((size_t)cd.w[1] << 6);
+      DVec tv;
+      tv.wf = cd.ts_cls() == FDB_FD_PACKED ? FDB_WF_DDV
+            : cd.ts_cls() == FDB_FD_CONST ? FDB_WF_DDV_CONST : FDB_WF_PRIM64;
+      tv.idata = tp + (cd.ts_cls() == FDB_FD_PACKED
+                           ? FDB_DDV_OFF_INNER + FDB_PRIM_OFF_DATA : FDB_PRIM_OFF_DATA);
+      tv.init = ts0 + cd.ts_base();     // d_decode_ts_offsets takes init - ts0
+      tv.slope = cd.ts_slope();
+      tv.n = n; tv.nbits = (uint8_t)cd.ts_nbits();
+      tv.sign = (cd.ts_flags() & FDB_FD_SIGN) != 0; tv.dropped = 0;
+      d_decode_ts_offsets(tv, n, ts0, ws.tso, dl);
+      const int vcls = cd.val_cls(), vbits = cd.val_nbits();
+      const bool vsign = (cd.val_flags() & FDB_FD_SIGN) != 0;
+      const bool exact32 = (cd.val_flags() & FDB_FD_EXACT32) != 0;
+      const uint8_t* vdata = vp + FDB_DDV_OFF_INNER + FDB_PRIM_OFF_DATA;
+      if (vcls == FDB_FD_PACKED && vbits == 8) {
+        d_decode_val4<8>(vdata, vsign, cd.val_init(), cd.val_slope(), exact32,
+                         n, ws.val, dl);
+      } else if (vcls == FDB_FD_PACKED && vbits == 16) {
+        d_decode_val4<16>(vdata, vsign, cd.val_init(), cd.val_slope(), exact32,
+                          n, ws.val, dl);
+      } else {        // const DDV, raw f64, packed 2/4/32-bit: the common decoder
+        DVec vv;
+        vv.wf = vcls == FDB_FD_PACKED ? FDB_WF_DDV
+              : vcls == FDB_FD_CONST ? FDB_WF_DDV_CONST : FDB_WF_PRIM64;
+        vv.idata = vcls == FDB_FD_PACKED ? vdata : vp + FDB_PRIM_OFF_DATA;
+        vv.init = cd.val_init(); vv.slope = cd.val_slope();
+        vv.n = n; vv.nbits = (uint8_t)vbits; vv.sign = vsign; vv.dropped = dropped;
+        d_decode_chunk<true>(vv, n, nullptr, ws.val, dl);
       }
-      n = nrows;
-      if (n > FDB_DEFAULT_MAX_ROWS || n > tv.n) { n = 0; ts0 = 0; }   // guarded at upload
-      if (n > 0) {
-        d_decode_ts_offsets(tv, n, ts0, ws.tso, lane);
-        d_decode_chunk<true>(vv, n, nullptr, ws.val, lane);
-        dropped = vv.dropped;
-      }
-    }
-    // prefetch stage 2: next series' chunk offsets (nfirst landed during the
-    // decode above; these land during this series' meta/window phases)
-    if (PF && npos < pos1) {
-      pf_sid = nsid; pf_first = nfirst; pf_nch = nnch;
-      pf_toff = dir.ts_off[nfirst];
-      pf_voff = dir.val_off[nfirst];
-      pf_nr = dir.num_rows[nfirst];
     }
     d_wait_lds();
     __builtin_amdgcn_wave_barrier();
@@ -673,14 +711,6 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
       __builtin_amdgcn_wave_barrier();
       if (timing) { uint64_t t = __builtin_amdgcn_s_memtime(); tW += t - tt; tt = t; }
     }  // tiles
-    // prefetch stage 3: next series' 32-B vector headers (the stage-2 offset
-    // loads landed during the window phase; these fly across the loop edge so
-    // the next decode starts with only the payload round-trip outstanding)
-    pf_hdr = PF && npos < pos1 && pf_nch >= 1;
-    if (pf_hdr) {
-      d_vec_open_wide(blob + pf_toff, &pf_tv, &pf_ts0);
-      d_vec_open_wide(blob + pf_voff, &pf_vv, nullptr);
-    }
   }  // series
   if (EMIT == 1 && cur_grp >= 0) flush_group(cur_grp);
   if (timing && EMIT == 0 && lane == 0) {
@@ -695,8 +725,8 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
 // ---------------------------------------------------------------------------
 // host-side launcher (called from engine.hip's launch dispatch)
 // ---------------------------------------------------------------------------
-int32_t fdb_launch_fast_scan(hipStream_t stream, const uint8_t* blob, DirSoA dir,
-                             const int32_t* series_first, const int32_t* series_nchunks,
+int32_t fdb_launch_fast_scan(hipStream_t stream, const uint8_t* blob,
+                             const FdbFastDesc* desc,
                              const int32_t* group_ids, const int32_t* series_by_group,
                              int num_series,
                              int64_t qstart, int64_t qstep, int64_t qwindow,
@@ -709,7 +739,7 @@ int32_t fdb_launch_fast_scan(hipStream_t stream, const uint8_t* blob, DirSoA dir
   if (const char* g = getenv("FDB_GRID")) cap = atoi(g);   // perf experiments
   if (cap > 0 && grid > cap) grid = cap;
   const char* rw = getenv("FDB_RATE_WAVES");   // occupancy experiment knob
-  const int rate_w = rw ? atoi(rw) : 7;   // 7-wave prefetch-free measured best (2.03 vs 2.07 ms at 6)
+  const int rate_w = rw ? atoi(rw) : 7;   // 7 measured best (rounds 3 and 4)
   // windows share end searches when the window is m = 1..64 whole steps
   // (FDB_WINDOW_SHARE=0: the two-searches-per-window path, for A/B runs)
   int wshare = 0;
@@ -717,32 +747,31 @@ int32_t fdb_launch_fast_scan(hipStream_t stream, const uint8_t* blob, DirSoA dir
       qwindow / qstep <= 64)
     wshare = (int)(qwindow / qstep);
   if (const char* s = getenv("FDB_WINDOW_SHARE")) { if (atoi(s) == 0) wshare = 0; }
-  // one launch of <F, EMIT, MINW, TIMED, PF>, SHARE picked by wshare
-  #define LAUNCH5(F, E, W, T, P) do { \
-    if (wshare) hipLaunchKernelGGL((fast_scan_kernel<F, E, W, T, P, true>), \
+  // one launch of <F, EMIT, MINW, TIMED>, SHARE picked by wshare
+  #define LAUNCH4(F, E, W, T) do { \
+    if (wshare) hipLaunchKernelGGL((fast_scan_kernel<F, E, W, T, true>), \
         dim3(grid), dim3(FAST_WAVES * 64), 0, stream, FARGS); \
-    else hipLaunchKernelGGL((fast_scan_kernel<F, E, W, T, P, false>), \
+    else hipLaunchKernelGGL((fast_scan_kernel<F, E, W, T, false>), \
         dim3(grid), dim3(FAST_WAVES * 64), 0, stream, FARGS); } while (0)
-  #define FARGS blob, dir, series_first, series_nchunks, group_ids, \
+  #define FARGS blob, desc, group_ids, \
       series_by_group, num_series, qstart, qstep, qwindow, num_windows, \
       agg_id, out, out_cnt, out_sq, phase_mask, wshare
-  #define LAUNCH(F, E, W) LAUNCH5(F, E, W, false, true)
+  #define LAUNCH(F, E, W) LAUNCH4(F, E, W, false)
   #define FCASE(F, W) case F: \
     if (emit_group) LAUNCH(F, 1, 4); else LAUNCH(F, 0, W); break
   const bool timed = (phase_mask & 8) != 0;   // s_memtime phase ablation
   switch (func_id) {
     case FN_RATE:
       if (emit_group) LAUNCH(FN_RATE, 1, 4);
-      else if (timed) LAUNCH5(FN_RATE, 0, 5, true, true);
-      else if (rate_w == 6)   // 6 waves/SIMD: prefetch stripped (register diet)
-        LAUNCH5(FN_RATE, 0, 6, false, false);
+      else if (timed) LAUNCH4(FN_RATE, 0, 7, true);   // the shipped default, timed
+      else if (rate_w == 6) LAUNCH(FN_RATE, 0, 6);
       else if (rate_w == 7)   // LDS fits 7 blocks/CU; needs <= 72 VGPRs
-        LAUNCH5(FN_RATE, 0, 7, false, false);
+        LAUNCH(FN_RATE, 0, 7);
       else LAUNCH(FN_RATE, 0, 5);
       break;
     case FN_AVG:
       if (emit_group) LAUNCH(FN_AVG, 1, 4);
-      else if (timed) LAUNCH5(FN_AVG, 0, 5, true, true);
+      else if (timed) LAUNCH4(FN_AVG, 0, 6, true);
       else LAUNCH(FN_AVG, 0, 6);
       break;
     FCASE(FN_INCREASE, 6); FCASE(FN_DELTA, 6); FCASE(FN_SUM, 6);
@@ -750,19 +779,14 @@ int32_t fdb_launch_fast_scan(hipStream_t stream, const uint8_t* blob, DirSoA dir
     FCASE(FN_MIN, 6); FCASE(FN_MAX, 6); FCASE(FN_STDDEV, 3); FCASE(FN_STDVAR, 3);
     FCASE(FN_CHANGES, 6); FCASE(FN_LAST, 6); FCASE(FN_PRESENT, 6);
     FCASE(FN_TIMESTAMP, 6); FCASE(FN_ZSCORE, 6);
-    FCASE(FN_IRATE, 6); FCASE(FN_IDELTA, 6);
-    case FN_RESETS:   // prefetch-free like the 6/7-wave rate builds: with the
-      // prefetch registers the shared search spills 2 VGPRs at 6 waves/SIMD
-      if (emit_group) LAUNCH(FN_RESETS, 1, 4);
-      else LAUNCH5(FN_RESETS, 0, 6, false, false);
-      break;
+    FCASE(FN_IRATE, 6); FCASE(FN_IDELTA, 6); FCASE(FN_RESETS, 6);
     default:
       fdb_set_error("fast scan: unsupported func_id %d", func_id);
       return FDB_ERR_BADARG;
   }
   #undef FCASE
   #undef LAUNCH
-  #undef LAUNCH5
+  #undef LAUNCH4
   #undef FARGS
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {

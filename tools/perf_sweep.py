@@ -59,7 +59,9 @@ def main():
         ms = bench(eng, ds, q_sum, gout, gcnt)
         print(f"sum-by-group fused={fused}: {ms:.3f} ms", flush=True)
     os.environ.pop("FDB_FUSED_GROUP")
-    # phase split (s_memtime; pm bit 3 clobbers out[] with per-wave cycles)
+    # phase split (s_memtime; pm bit 3 clobbers out[] with per-wave cycles):
+    # the launcher's timed instantiation is the shipped rate build itself
+    # (7 waves/SIMD, shared window search), result stores suppressed
     q_rate._pad = 8
     eng.query(ds, q_rate, out=out, on_device=True)
     eng.synchronize()
