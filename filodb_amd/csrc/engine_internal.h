@@ -11,6 +11,7 @@
 
 #include "chunk_format.h"
 #include "scan_common.h"
+#include "window_funcs.h"
 #include "../../include/filodb_amd.h"
 
 void fdb_set_error(const char* fmt, ...);         // chunk_builder.cpp

@@ -30,6 +30,15 @@
 
 #define H2_WAVES 4
 
+// wave-wide inclusive prefix sum over i64 (bucket-cumulative reconstruction)
+__device__ __forceinline__ int64_t wave_incl_scan_i64(int64_t x, int lane) {
+  for (int off = 1; off < 64; off <<= 1) {
+    int64_t t = __shfl_up(x, off);
+    if (lane >= off) x += t;
+  }
+  return x;
+}
+
 // parse one element's per-lane bucket delta from its NibblePack stream.
 // ep = element start (at the u16 length); wave-uniform. All lanes must be
 // active (estream shuffles). Returns the lane's (<<trailing-zeroes) delta.

@@ -1,5 +1,6 @@
 // Shared device-side pieces of the MI355X scan engine: frozen-vector readers,
-// wave scans, the extrapolatedRate epilogue and launch plumbing types.
+// chunk decoders, wave scans and launch plumbing types (window_funcs.h has
+// the range functions' per-window rules).
 // Layouts: DESIGN.md §2 (bit-faithful to the reference's off-heap vectors).
 #ifndef FDB_SCAN_COMMON_H
 #define FDB_SCAN_COMMON_H
@@ -66,6 +67,11 @@ __device__ __forceinline__ int64_t d_inner_at(const DVec* v, int i) {
 // flying across the fence
 __device__ __forceinline__ void d_wait_lds() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+// the wave's LDS writes so far are visible to all of its lanes
+__device__ __forceinline__ void d_lds_fence() {
+  d_wait_lds();
+  __builtin_amdgcn_wave_barrier();
 }
 
 __device__ __forceinline__ int64_t d_lv_at(const DVec* v, int i) {
@@ -364,73 +370,6 @@ __device__ inline void d_decode_ts_offsets(const DVec& v, int n, int64_t ts0,
                         + (uint32_t)d_inner_at(&v, i));
 }
 
-// Correctly-rounded x/1000 in 3 ops (mul + 2 fma, Markstein fixup) instead of
-// the ~10-instruction v_div_scale/v_div_fmas/v_div_fixup sequence. EXACTLY
-// equal to RN(x/1000) for every integer |x| <= 2^33 — verified exhaustively
-// (8.59e9 cases, 0 mismatches; the naive q0 = x*(1/1000) alone differs on 13%
-// of them). Callers pass integer millisecond DIFFERENCES bounded by the
-// window length; the engine rejects windows > 2^33 ms (~99 days) up front.
-__device__ __forceinline__ double d_div1000(double x) {
-  constexpr double r = 1.0 / 1000.0;                // RN reciprocal
-  double q0 = x * r;
-  double e = __builtin_fma(-1000.0, q0, x);         // exact residual
-  return __builtin_fma(e, r, q0);
-}
-
-// extrapolatedRate (RateFunctions.scala:72-111) — the oracle's EXACT
-// operation sequence. Do not reassociate or replace the divisions: the
-// durationToZero/threshold comparisons are discontinuous and integer counter
-// data makes exact rational ties (v1/delta == 1.1/(numSamples-1)) common, so
-// the branch taken must follow the reference's own FP rounding. (The /1000
-// sites use d_div1000 — bit-identical on the engine's ms-difference domain.)
-__device__ inline double d_extrapolated_rate(int64_t windowStart, int64_t windowEnd,
-                                             int numSamples,
-                                             int64_t t1, double v1, int64_t t2, double v2,
-                                             bool isCounter, bool isRate) {
-  double durationToStart = d_div1000((double)(t1 - windowStart));
-  double durationToEnd = d_div1000((double)(windowEnd - t2));
-  double sampledInterval = d_div1000((double)(t2 - t1));
-  double avgDur = sampledInterval / ((double)numSamples - 1);
-  double delta = v2 - v1;
-  if (isCounter && delta > 0 && v1 >= 0) {
-    double durationToZero = sampledInterval * (v1 / delta);
-    if (durationToZero < durationToStart) durationToStart = durationToZero;
-  }
-  double thresh = avgDur * 1.1;
-  double ext = sampledInterval;
-  ext += (durationToStart < thresh) ? durationToStart : avgDur / 2;
-  ext += (durationToEnd < thresh) ? durationToEnd : avgDur / 2;
-  double scaledDelta = delta * (ext / sampledInterval);
-  return isRate ? (scaledDelta / (double)(windowEnd - windowStart) * 1000.0) : scaledDelta;
-}
-
-// i32-difference variant of d_extrapolated_rate for the fast path: all three
-// millisecond gaps fit i32 when the window does (caller checks), so each
-// i64 subtract + 4-instruction i64→f64 convert becomes a truncate + single
-// v_cvt_f64_i32; the window duration is wave-uniform and passed pre-converted.
-// Every operation after the converts matches d_extrapolated_rate exactly
-// (same values, same rounding) — results are bit-identical.
-__device__ inline double d_extrapolated_rate_i32(int32_t toStart_ms, int32_t toEnd_ms,
-                                                 int numSamples, int32_t sampled_ms,
-                                                 double dur_ms, double v1, double v2,
-                                                 bool isCounter, bool isRate) {
-  double durationToStart = d_div1000((double)toStart_ms);
-  double durationToEnd = d_div1000((double)toEnd_ms);
-  double sampledInterval = d_div1000((double)sampled_ms);
-  double avgDur = sampledInterval / ((double)numSamples - 1);
-  double delta = v2 - v1;
-  if (isCounter && delta > 0 && v1 >= 0) {
-    double durationToZero = sampledInterval * (v1 / delta);
-    if (durationToZero < durationToStart) durationToStart = durationToZero;
-  }
-  double thresh = avgDur * 1.1;
-  double ext = sampledInterval;
-  ext += (durationToStart < thresh) ? durationToStart : avgDur / 2;
-  ext += (durationToEnd < thresh) ? durationToEnd : avgDur / 2;
-  double scaledDelta = delta * (ext / sampledInterval);
-  return isRate ? (scaledDelta / dur_ms * 1000.0) : scaledDelta;
-}
-
 // NaN-aware f64 atomic min/max via CAS (group aggregation; RowAggregator semantics)
 __device__ inline void atomic_min_max_f64(double* addr, double val, bool is_min) {
   unsigned long long* a = (unsigned long long*)addr;
@@ -442,15 +381,6 @@ __device__ inline void atomic_min_max_f64(double* addr, double val, bool is_min)
     if (!isnan(cur) && nw == cur) return;
     old = atomicCAS(a, assumed, (unsigned long long)__double_as_longlong(nw));
   } while (old != assumed);
-}
-
-// wave-wide inclusive prefix sum over i64 (bucket-cumulative reconstruction)
-__device__ __forceinline__ int64_t wave_incl_scan_i64(int64_t x, int lane) {
-  for (int off = 1; off < 64; off <<= 1) {
-    int64_t t = __shfl_up(x, off);
-    if (lane >= off) x += t;
-  }
-  return x;
 }
 
 // --- wave-staged element stream -------------------------------------------
@@ -514,6 +444,5 @@ __device__ __forceinline__ uint64_t estream_w64(bool staged, uint32_t buf,
   memcpy(&w, g + k, 8);
   return w;
 }
-
 
 #endif  // FDB_SCAN_COMMON_H

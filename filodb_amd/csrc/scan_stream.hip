@@ -74,8 +74,7 @@ void summary_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
       d_decode_chunk<false>(tv, n, ts, nullptr, lane);
       d_decode_chunk<true>(vv, n, nullptr, val, lane);
     }
-    d_wait_lds();
-    __builtin_amdgcn_wave_barrier();
+    d_lds_fence();
 
     ChunkSum s;
     memset(&s, 0, sizeof(s));
@@ -84,10 +83,7 @@ void summary_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
       double sum = 0, sq = 0, mn = NAN, mx = NAN;
       int cnt = 0, changes = 0, resets = 0;
       double carry_raw = NAN;                 // previous row's raw value
-      double corr_carry = 0;                  // drop-scan carries
-      double corr_x = -1.7976931348623157e308;
-      int ndrops = 0;
-      bool dense = false;
+      ResetScan rs;
       const bool dropped = vv.dropped != 0;
       double last_nonnan = 0;                 // last_for_update when dropped
       int last_nonnan_idx = -1;
@@ -100,38 +96,19 @@ void summary_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
         sum += x;                              // lane partials; reduced below
         sq += x * x;
         cnt += ok ? 1 : 0;
-        if (ok && (isnan(mn) || raw < mn)) mn = raw;
-        if (ok && (isnan(mx) || raw > mx)) mx = raw;
-        // interior changes (DoubleVectorDataReader64.changes :283-302)
+        d_fold_mm<true>(mn, raw);              // raw is NaN past the chunk
+        d_fold_mm<false>(mx, raw);
+        // interior changes and resets (raw is NaN past the chunk)
         double px = __shfl_up(raw, 1);
         if (lane == 0) px = carry_raw;
-        changes += (i > 0 && live && !isnan(raw) && !isnan(px) && raw != px)
-                       ? 1 : 0;
-        // interior resets (ResetsFunction, RangeInstantFunctions.scala:355-365)
-        resets += (i > 0 && live && !isnan(raw) && !isnan(px) && raw < px)
-                      ? 1 : 0;
+        changes += (i > 0 && d_pair_counts<false>(raw, px)) ? 1 : 0;
+        resets += (i > 0 && d_pair_counts<true>(raw, px)) ? 1 : 0;
         carry_raw = __shfl(raw, 63);
-        // counter-reset scan (NaN→0; CorrectingDoubleVectorReader :325-342);
-        // table slots published through LDS so lane 0 can emit them
+        // counter-reset scan; table slots published through LDS so lane 0
+        // can emit them
         if (dropped) {
-          double pz = __shfl_up(x, 1);
-          if (lane == 0) pz = corr_x;
-          double ci = (live && x < pz) ? pz : 0;
-          double scan = wave_incl_scan(ci, lane);
-          uint64_t mask = __ballot(ci != 0);
-          int here = __popcll(mask);
-          if (here) {
-            if (ndrops + here > SUM_DROPS) {
-              dense = true;
-            } else if (ci != 0) {
-              int slot = ndrops + __popcll(mask & ((1ULL << lane) - 1));
-              dpos_all[wave][slot] = (int16_t)i;
-              dcum_all[wave][slot] = corr_carry + scan;
-            }
-            if (!dense) ndrops += here;
-          }
-          corr_carry += __shfl(scan, 63);
-          corr_x = __shfl(x, 63);
+          d_reset_scan_step<SUM_DROPS>(rs, i, live, x, lane,
+                                       dpos_all[wave], dcum_all[wave]);
           if (ok) { last_nonnan_idx = i; last_nonnan = raw; }
         }
       }
@@ -141,16 +118,13 @@ void summary_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
         cnt += __shfl_down(cnt, off);
         changes += __shfl_down(changes, off);
         resets += __shfl_down(resets, off);
-        double o = __shfl_down(mn, off);
-        if (!isnan(o) && (isnan(mn) || o < mn)) mn = o;
-        o = __shfl_down(mx, off);
-        if (!isnan(o) && (isnan(mx) || o > mx)) mx = o;
+        d_fold_mm<true>(mn, __shfl_down(mn, off));
+        d_fold_mm<false>(mx, __shfl_down(mx, off));
         int oi = __shfl_down(last_nonnan_idx, off);
         double ov = __shfl_down(last_nonnan, off);
         if (oi > last_nonnan_idx) { last_nonnan_idx = oi; last_nonnan = ov; }
       }
-      d_wait_lds();
-      __builtin_amdgcn_wave_barrier();
+      d_lds_fence();
       s.ts0 = ts[0];
       s.ts_last = ts[n - 1];
       s.sum = sum; s.sqsum = sq; s.cnt = cnt; s.changes_in = changes;
@@ -160,51 +134,43 @@ void summary_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
       s.last_val = val[n - 1];
       s.v0_nan = isnan(val[0]) ? 1 : 0;
       s.dropped = dropped ? 1 : 0;
-      s.dense = dense ? 1 : 0;
-      s.ndrops = (uint8_t)(dense ? 0 : ndrops);
-      s.chunk_corr = corr_carry;
+      s.dense = rs.dense ? 1 : 0;
+      s.ndrops = (uint8_t)(rs.dense ? 0 : rs.count);
+      s.chunk_corr = rs.carry_corr;
       s.last_for_update = dropped ? (last_nonnan_idx >= 0 ? last_nonnan : 0)
                                   : val[n - 1];
       s.inv_slope = (s.ts_last > s.ts0)
                         ? (float)(n - 1) / (float)(s.ts_last - s.ts0) : 0.0f;
-      if (!dense) {
-        for (int j = 0; j < ndrops; j++) {
+      if (!rs.dense) {
+        for (int j = 0; j < rs.count; j++) {
           s.dpos[j] = dpos_all[wave][j];
           s.dcum[j] = dcum_all[wave][j];
         }
       }
     }
     if (lane == 0) out[c] = s;
-    d_wait_lds();
-    __builtin_amdgcn_wave_barrier();
+    d_lds_fence();
   }
 }
 
 // ---------------------------------------------------------------------------
 // global-memory row access for the walk kernel's boundary ranges
 // ---------------------------------------------------------------------------
-// in-chunk corrected value at row (CorrectingDoubleVectorReader :305-392):
-// raw NaN→0 plus the correction step function from the sparse table, or a
-// serial recompute when the chunk overflowed the table
+// in-chunk corrected value at row: raw NaN→0 plus the chunk's correction
 __device__ double g_corrected(const DVec& vv, const ChunkSum& cs, int row) {
   double x = d_dv_at(&vv, row);
   if (!cs.dropped) return x;
   if (isnan(x)) x = 0;
-  if (cs.dense) {
-    double corr = 0, last = -1.7976931348623157e308;
-    for (int j = 0; j <= row; j++) {
-      double v = d_dv_at(&vv, j);
-      if (isnan(v)) v = 0;
-      if (v < last) corr += last;
-      last = v;
-    }
-    return x + corr;
-  }
-  double corr = 0;
-  for (int j = 0; j < cs.ndrops; j++) {
-    if (cs.dpos[j] <= row) corr = cs.dcum[j]; else break;
-  }
-  return x + corr;
+  return x + d_corr_at(cs.dpos, cs.dcum, cs.ndrops, cs.dense, row,
+                       [&](int j) { return d_dv_at(&vv, j); });
+}
+
+// one chunk's row range for a window, searched with its summary's endpoints
+__device__ __forceinline__ ChunkRows walk_rows(const uint8_t* blob, const DirSoA& dir,
+                                               const ChunkSum& cs, int chunk,
+                                               int64_t wStart, int64_t wEnd) {
+  return d_chunk_rows(blob, dir, chunk, wStart, wEnd, &cs.ts0, cs.ts_last,
+                      [&](int, int64_t) { return cs.inv_slope; });
 }
 
 // ---------------------------------------------------------------------------
@@ -244,16 +210,11 @@ void stream_walk_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
         constexpr bool isCounter = (FUNC != FN_DELTA);
         for (int c = 0; c < nchunks; c++) {
           const int64_t cend = dir.end_time[first + c];
-          if (cend < wStart) continue;        // WindowedChunkIterator drop rule
+          if (d_chunk_before_window(cend, wStart)) continue;
           const ChunkSum& cs = sums[first + c];
-          const int n = dir.num_rows[first + c];
-          DVec tv, vv;
-          d_vec_open_wide(blob + dir.ts_off[first + c], &tv, nullptr);
-          d_vec_open_wide(blob + dir.val_off[first + c], &vv, nullptr);
-          int startRow = (wStart <= cs.ts0) ? 0
-              : d_search_ge(tv, n, wStart, cs.ts0, cs.inv_slope);
-          int endRow = (wEnd >= cs.ts_last) ? n - 1
-              : d_search_ge(tv, n, wEnd + 1, cs.ts0, cs.inv_slope) - 1;
+          const ChunkRows r = walk_rows(blob, dir, cs, first + c, wStart, wEnd);
+          const DVec &tv = r.tv, &vv = r.vv;
+          const int n = r.n, startRow = r.startRow, endRow = r.endRow;
           if (isCounter && meta_has) {        // detectDropAndCorrection
             double firstv = cs.first_val;
             if (isnan(firstv) || firstv < meta_last) meta_corr += meta_last;
@@ -285,7 +246,7 @@ void stream_walk_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
             meta_last = cs.last_for_update;
             meta_has = true;
           }
-          if (cend >= wEnd) break;            // add-while rule
+          if (d_chunk_ends_walk(cend, wEnd)) break;
         }
         if (highestTime > lowestTime)
           result = d_extrapolated_rate(wStart, wEnd, numSamples,
@@ -300,16 +261,11 @@ void stream_walk_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
         int icount = 0;
         for (int c = 0; c < nchunks; c++) {
           const int64_t cend = dir.end_time[first + c];
-          if (cend < wStart) continue;
+          if (d_chunk_before_window(cend, wStart)) continue;
           const ChunkSum& cs = sums[first + c];
-          const int n = dir.num_rows[first + c];
-          DVec tv, vv;
-          d_vec_open_wide(blob + dir.ts_off[first + c], &tv, nullptr);
-          d_vec_open_wide(blob + dir.val_off[first + c], &vv, nullptr);
-          int startRow = (wStart <= cs.ts0) ? 0
-              : d_search_ge(tv, n, wStart, cs.ts0, cs.inv_slope);
-          int endRow = (wEnd >= cs.ts_last) ? n - 1
-              : d_search_ge(tv, n, wEnd + 1, cs.ts0, cs.inv_slope) - 1;
+          const ChunkRows r = walk_rows(blob, dir, cs, first + c, wStart, wEnd);
+          const DVec &tv = r.tv, &vv = r.vv;
+          const int n = r.n, startRow = r.startRow, endRow = r.endRow;
 
           if constexpr (FUNC == FN_LAST || FUNC == FN_PRESENT) {
             // LastSampleChunkedFunction.addChunks (RangeFunction.scala:599-614)
@@ -318,80 +274,47 @@ void stream_walk_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
               if (t >= wStart && t > last_ts) {
                 double v = d_dv_at(&vv, endRow);
                 if (FUNC == FN_LAST) { last_ts = t; last_val = v; }
-                else if (!isnan(v)) { last_ts = t; last_val = 1.0; }
-                else if (endRow > 0) {
+                else if (d_present_at(v, endRow, [&](int j) { return d_dv_at(&vv, j); },
+                                      &last_val))
                   last_ts = t;
-                  last_val = isnan(d_dv_at(&vv, endRow - 1)) ? NAN : 1.0;
-                }
               }
             }
-            if (cend >= wEnd) break;
-            continue;
-          }
-          if constexpr (FUNC == FN_TIMESTAMP) {
+          } else if constexpr (FUNC == FN_TIMESTAMP) {
             if (endRow >= 0 && endRow < n) {
               int64_t t = (endRow == n - 1) ? cs.ts_last : d_lv_at(&tv, endRow);
               if (t > last_ts) { last_ts = t; last_val = (double)t / 1000.0; }
             }
-            if (cend >= wEnd) break;
-            continue;
-          }
-
-          if (startRow <= endRow && endRow < n) {
+          } else if (startRow <= endRow && endRow < n) {
             const bool full = (startRow == 0 && endRow == n - 1);
-            if constexpr (FUNC == FN_SUM || FUNC == FN_AVG ||
-                          FUNC == FN_RATE_OVER_DELTA || FUNC == FN_COUNT) {
-              double csum; int cc;
-              if (full) { csum = cs.cnt > 0 ? cs.sum : NAN; cc = cs.cnt; }
-              else {
-                csum = NAN; cc = 0;
-                for (int i = startRow; i <= endRow; i++) {
-                  double x = d_dv_at(&vv, i);
-                  if (isnan(x)) continue;
-                  if (isnan(csum)) csum = 0;
-                  csum += x; cc++;
-                }
-              }
+            constexpr bool VAR_FAMILY =
+                (FUNC == FN_STDDEV || FUNC == FN_STDVAR || FUNC == FN_ZSCORE);
+            if constexpr (FUNC == FN_SUM || FUNC == FN_AVG || FUNC == FN_COUNT ||
+                          FUNC == FN_RATE_OVER_DELTA || VAR_FAMILY) {
+              // the range's NaN-skipping moments: a whole chunk's from its summary
+              double csm = NAN, csq = NAN; int cc = 0;
+              if (!full)
+                d_range_moments([&](int j) { return d_dv_at(&vv, j); },
+                                startRow, endRow, csm, csq, cc);
+              else if (cs.cnt > 0) { csm = cs.sum; csq = cs.sqsum; cc = cs.cnt; }
               if constexpr (FUNC == FN_COUNT) {
                 if (isnan(sum)) sum = 0;     // CountOverTime: any range starts 0
                 sum += (double)cc;
               } else {
-                if (!isnan(csum) && isnan(sum)) sum = 0;
-                sum += csum;                  // NaN-poison quirk preserved
+                d_poison_add(sum, csm);       // NaN-poison quirk preserved
                 icount += cc;
+              }
+              if constexpr (VAR_FAMILY) {
+                // VarOverTimeChunkedFunctionD :1082-1115; last_sample set only
+                // from a non-NaN range end (:1103)
+                d_poison_add(sqsum, csq);
+                const double end_raw = full ? cs.last_val : d_dv_at(&vv, endRow);
+                if (!isnan(end_raw)) last_sample = end_raw;
               }
             } else if constexpr (FUNC == FN_MIN || FUNC == FN_MAX) {
               constexpr bool IS_MIN = (FUNC == FN_MIN);
-              auto acc = [&](double x) {
-                if (!isnan(x) && (isnan(mm) || (IS_MIN ? x < mm : x > mm)))
-                  mm = x;
-              };
-              if (full) acc(IS_MIN ? cs.vmin : cs.vmax);
-              else for (int i = startRow; i <= endRow; i++) acc(d_dv_at(&vv, i));
-            } else if constexpr (FUNC == FN_STDDEV || FUNC == FN_STDVAR ||
-                                 FUNC == FN_ZSCORE) {
-              // VarOverTimeChunkedFunctionD :1082-1115; last_sample set only
-              // from a non-NaN range end (:1103)
-              double csm = NAN, csq = NAN; int cc = 0;
-              double end_raw;
-              if (full) {
-                if (cs.cnt > 0) { csm = cs.sum; csq = cs.sqsum; cc = cs.cnt; }
-                end_raw = cs.last_val;
-              } else {
-                for (int i = startRow; i <= endRow; i++) {
-                  double x = d_dv_at(&vv, i);
-                  if (isnan(x)) continue;
-                  if (isnan(csm)) { csm = 0; csq = 0; }
-                  csm += x; csq += x * x; cc++;
-                }
-                end_raw = d_dv_at(&vv, endRow);
-              }
-              if (!isnan(end_raw)) last_sample = end_raw;
-              if (!isnan(csm) && isnan(sum)) sum = 0;
-              sum += csm;
-              if (!isnan(csq) && isnan(sqsum)) sqsum = 0;
-              sqsum += csq;
-              icount += cc;
+              if (full) d_fold_mm<IS_MIN>(mm, IS_MIN ? cs.vmin : cs.vmax);
+              else for (int i = startRow; i <= endRow; i++)
+                d_fold_mm<IS_MIN>(mm, d_dv_at(&vv, i));
             } else if constexpr (FUNC == FN_IRATE || FUNC == FN_IDELTA) {
               // the window's last two rows: a range of >= 2 rows supplies
               // both, a 1-row range shifts last -> prev (the previous sample
@@ -406,7 +329,7 @@ void stream_walk_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
               last_ts = (endRow == n - 1) ? cs.ts_last : d_lv_at(&tv, endRow);
               last_val = (endRow == n - 1) ? cs.last_val : d_dv_at(&vv, endRow);
               icount += rn;
-            } else {  // FN_CHANGES / FN_RESETS: x != p / x < p, NaN never counts
+            } else {  // FN_CHANGES / FN_RESETS
               constexpr bool IS_RESETS = (FUNC == FN_RESETS);
               if (isnan(changes)) changes = 0;
               double first_raw, last_raw;
@@ -419,21 +342,19 @@ void stream_walk_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
                 double p = NAN;
                 for (int i = startRow; i <= endRow; i++) {
                   double x = d_dv_at(&vv, i);
-                  if (i > startRow && !isnan(x) && !isnan(p) &&
-                      (IS_RESETS ? x < p : x != p)) ch += 1;
+                  if (i > startRow && d_pair_counts<IS_RESETS>(x, p)) ch += 1;
                   p = x;
                 }
                 first_raw = d_dv_at(&vv, startRow);
                 last_raw = p;
               }
-              if (!isnan(first_raw) && !isnan(prev) &&
-                  (IS_RESETS ? first_raw < prev : first_raw != prev))
+              if (d_pair_counts<IS_RESETS>(first_raw, prev))
                 ch += 1;                      // cross-chunk boundary pair
               changes += ch;
               prev = last_raw;
             }
           }
-          if (cend >= wEnd) break;
+          if (d_chunk_ends_walk(cend, wEnd)) break;
         }
         switch (FUNC) {
           case FN_SUM: result = sum; break;
@@ -446,39 +367,23 @@ void stream_walk_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
             result = icount > 0 ? sum / icount : (isnan(sum) ? sum : 0);
             break;
           case FN_MIN: case FN_MAX: result = mm; break;
-          case FN_STDDEV: case FN_STDVAR: {
-            if (icount > 0) {
-              double avg = sum / icount;
-              double r = sqsum / icount - avg * avg;
-              result = (FUNC == FN_STDDEV) ? sqrt(r) : r;
-            } else result = isnan(sum) ? sum : 0;
-          } break;
+          case FN_STDDEV: case FN_STDVAR:
+            result = d_var_finish(sum, sqsum, icount, FUNC == FN_STDDEV);
+            break;
           case FN_CHANGES: case FN_RESETS: result = changes; break;
           case FN_IDELTA:
             // instantValue(isRate=false), RangeInstantFunctions.scala:68-95
             if (icount >= 2) result = last_val - prev;
             break;
           case FN_IRATE:
-            // instantValue(isRate=true) over counter-corrected rows with the
-            // common correction cancelled: NaN -> 0, a drop
-            // yields last; one divide, then one multiply
-            if (icount >= 2) {
-              const double l = isnan(last_val) ? 0 : last_val;
-              const double p = isnan(prev) ? 0 : prev;
-              const double d = (l < p) ? l : l - p;
-              const double dt = (double)(last_ts - prev_ts);
-              result = (dt == 0) ? NAN : d / dt * 1000.0;
-            }
+            if (icount >= 2)
+              result = d_irate_finish(last_val, prev, (double)(last_ts - prev_ts));
             break;
           case FN_LAST: case FN_PRESENT: case FN_TIMESTAMP:
             result = last_val; break;
-          case FN_ZSCORE: {
-            if (icount > 0) {
-              double avg = sum / icount;
-              double sd = sqrt(sqsum / icount - avg * avg);
-              result = (last_sample - avg) / sd;
-            } else result = isnan(sum) ? sum : 0;
-          } break;
+          case FN_ZSCORE:
+            result = d_zscore_finish(sum, sqsum, icount, last_sample);
+            break;
         }
       }
       out[(size_t)sid * num_windows + w] = result;

@@ -34,6 +34,30 @@ __device__ __forceinline__ float ws_inv_slope(int n, int64_t ts0, int64_t tsl) {
   return (tsl > ts0) ? (float)(n - 1) / (float)(tsl - ts0) : 0.0f;
 }
 
+// wave-wide sum in tree order; every lane gets the total
+template <typename T>
+__device__ __forceinline__ T ws_wave_sum(T v) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+  return __shfl(v, 0);
+}
+
+// ascending bitonic sort of buf[0..m), m a power of two, by one wave
+__device__ __forceinline__ void ws_bitonic_sort(double* buf, int m, int lane) {
+  for (int k = 2; k <= m; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = lane; t < m; t += 64) {
+        int ixj = t ^ j;
+        if (ixj > t) {
+          double a = buf[t], b2 = buf[ixj];
+          bool up = ((t & k) == 0);
+          if ((a > b2) == up) { buf[t] = b2; buf[ixj] = a; }
+        }
+      }
+      d_lds_fence();
+    }
+  }
+}
+
 template <int FUNC>
 __global__ __launch_bounds__(WS_WAVES * 64)
 void window_sample_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
@@ -70,17 +94,12 @@ void window_sample_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
 
     for (int c = 0; c < nchunks; c++) {
       const int64_t cend = dir.end_time[first + c];
-      if (cend < wStart) continue;
-      DVec tv, vv;
-      int64_t ts0;
-      d_vec_open_wide(blob + dir.ts_off[first + c], &tv, &ts0);
-      d_vec_open_wide(blob + dir.val_off[first + c], &vv, nullptr);
-      const int n = dir.num_rows[first + c];
-      const int64_t tsl = dir.end_time[first + c];
-      int startRow = (wStart <= ts0) ? 0
-          : d_search_ge(tv, n, wStart, ts0, ws_inv_slope(n, ts0, tsl));
-      int endRow = (wEnd >= tsl) ? n - 1
-          : d_search_ge(tv, n, wEnd + 1, ts0, ws_inv_slope(n, ts0, tsl)) - 1;
+      if (d_chunk_before_window(cend, wStart)) continue;
+      const ChunkRows r = d_chunk_rows(    // ts0 from the header; cend = last ts
+          blob, dir, first + c, wStart, wEnd, nullptr, cend,
+          [&](int n, int64_t t0) { return ws_inv_slope(n, t0, cend); });
+      const DVec &tv = r.tv, &vv = r.vv;
+      const int n = r.n, startRow = r.startRow, endRow = r.endRow;
       if (startRow <= endRow && endRow < n) {
         touched = true;
         if constexpr (FUNC == FN_PREDICT_LINEAR) {
@@ -94,13 +113,8 @@ void window_sample_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
             double x = (double)(d_lv_at(&tv, i) - wEnd) / 1000.0;
             sx += x; sy += y; sxy += x * y; sx2 += x * x; cnt++;
           }
-          for (int off = 32; off > 0; off >>= 1) {
-            sx += __shfl_down(sx, off); sy += __shfl_down(sy, off);
-            sxy += __shfl_down(sxy, off); sx2 += __shfl_down(sx2, off);
-            cnt += __shfl_down(cnt, off);
-          }
-          sx = __shfl(sx, 0); sy = __shfl(sy, 0);
-          sxy = __shfl(sxy, 0); sx2 = __shfl(sx2, 0); cnt = __shfl(cnt, 0);
+          sx = ws_wave_sum(sx); sy = ws_wave_sum(sy);
+          sxy = ws_wave_sum(sxy); sx2 = ws_wave_sum(sx2); cnt = ws_wave_sum(cnt);
           if (cnt > 0) {
             if (isnan(plY)) { plY = sy; plX = sx; plXY = sxy; plX2 = sx2; }
             else { plY += sy; plX += sx; plXY += sxy; plX2 += sx2; }
@@ -113,19 +127,15 @@ void window_sample_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
           // so any NaN in the window gives NaN and n counts every row). No
           // sample buffer, so no cap on the window's rows.
           if (plN == 0)
-            drv_t0 = (startRow == 0) ? ts0 : d_lv_at(&tv, startRow);
+            drv_t0 = (startRow == 0) ? r.ts0 : d_lv_at(&tv, startRow);
           double sx = 0, sy = 0, sxy = 0, sx2 = 0;
           for (int i = startRow + lane; i <= endRow; i += 64) {
             double y = d_dv_at(&vv, i);
             double x = (double)(d_lv_at(&tv, i) - drv_t0) / 1000.0;
             sx += x; sy += y; sxy += x * y; sx2 += x * x;
           }
-          for (int off = 32; off > 0; off >>= 1) {
-            sx += __shfl_down(sx, off); sy += __shfl_down(sy, off);
-            sxy += __shfl_down(sxy, off); sx2 += __shfl_down(sx2, off);
-          }
-          sx = __shfl(sx, 0); sy = __shfl(sy, 0);
-          sxy = __shfl(sxy, 0); sx2 = __shfl(sx2, 0);
+          sx = ws_wave_sum(sx); sy = ws_wave_sum(sy);
+          sxy = ws_wave_sum(sxy); sx2 = ws_wave_sum(sx2);
           if (plN == 0) { plY = sy; plX = sx; plXY = sxy; plX2 = sx2; }
           else { plY += sy; plX += sx; plXY += sxy; plX2 += sx2; }
           plN += endRow - startRow + 1;
@@ -191,7 +201,7 @@ void window_sample_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
           if (over) break;
         }
       }
-      if (cend >= wEnd) break;
+      if (d_chunk_ends_walk(cend, wEnd)) break;
     }
 
     double result = NAN;
@@ -218,27 +228,12 @@ void window_sample_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
       else if (FUNC == FN_QUANTILE && touched && param > 1) result = INFINITY;
       else if (qn > 0) {
         // bitonic sort of buf[0..qn) padded to a power of two with +inf
-        d_wait_lds();
-        __builtin_amdgcn_wave_barrier();
+        d_lds_fence();
         int m = 1;
         while (m < qn) m <<= 1;
         for (int i = qn + lane; i < m; i += 64) buf[i] = INFINITY;
-        d_wait_lds();
-        __builtin_amdgcn_wave_barrier();
-        for (int k = 2; k <= m; k <<= 1) {
-          for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = lane; t < m; t += 64) {
-              int ixj = t ^ j;
-              if (ixj > t) {
-                double a = buf[t], b2 = buf[ixj];
-                bool up = ((t & k) == 0);
-                if ((a > b2) == up) { buf[t] = b2; buf[ixj] = a; }
-              }
-            }
-            d_wait_lds();
-            __builtin_amdgcn_wave_barrier();
-          }
-        }
+        d_lds_fence();
+        ws_bitonic_sort(buf, m, lane);
         // interp_quantile (oracle-exact): rank = q*(n-1)
         auto interp = [&](double q, int n2) {
           double rank = q * (n2 - 1);
@@ -252,33 +247,17 @@ void window_sample_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
           result = interp(param, qn);
         } else {  // FN_MAD: |median - x| re-sorted, median again
           double median = interp(0.5, qn);
-          d_wait_lds();
-          __builtin_amdgcn_wave_barrier();
+          d_lds_fence();
           for (int i = lane; i < qn; i += 64) buf[i] = fabs(median - buf[i]);
           for (int i = qn + lane; i < m; i += 64) buf[i] = INFINITY;
-          d_wait_lds();
-          __builtin_amdgcn_wave_barrier();
-          for (int k = 2; k <= m; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
-              for (int t = lane; t < m; t += 64) {
-                int ixj = t ^ j;
-                if (ixj > t) {
-                  double a = buf[t], b2 = buf[ixj];
-                  bool up = ((t & k) == 0);
-                  if ((a > b2) == up) { buf[t] = b2; buf[ixj] = a; }
-                }
-              }
-              d_wait_lds();
-              __builtin_amdgcn_wave_barrier();
-            }
-          }
+          d_lds_fence();
+          ws_bitonic_sort(buf, m, lane);
           result = interp(0.5, qn);
         }
       }
     }
     if (lane == 0) out[pair] = result;
-    d_wait_lds();
-    __builtin_amdgcn_wave_barrier();
+    d_lds_fence();
   }
 }
 
@@ -298,37 +277,21 @@ int32_t fdb_launch_window_sample(hipStream_t stream, const uint8_t* blob,
   size_t grid = (pairs + WS_WAVES - 1) / WS_WAVES;
   if (grid > 8192) grid = 8192;
   if (grid < 1) grid = 1;
-  #define WARGS blob, dir, series_first, series_nchunks, num_series, \
-      qstart, qstep, qwindow, num_windows, param, param2, out, overflow
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(WS_WAVES * 64), 0, stream,
+                       blob, dir, series_first, series_nchunks, num_series, qstart,
+                       qstep, qwindow, num_windows, param, param2, out, overflow);
+  };
   switch (func_id) {
-    case FN_QUANTILE:
-      hipLaunchKernelGGL((window_sample_kernel<FN_QUANTILE>), dim3((uint32_t)grid),
-                         dim3(WS_WAVES * 64), 0, stream, WARGS);
-      break;
-    case FN_MAD:
-      hipLaunchKernelGGL((window_sample_kernel<FN_MAD>), dim3((uint32_t)grid),
-                         dim3(WS_WAVES * 64), 0, stream, WARGS);
-      break;
-    case FN_PREDICT_LINEAR:
-      hipLaunchKernelGGL((window_sample_kernel<FN_PREDICT_LINEAR>),
-                         dim3((uint32_t)grid), dim3(WS_WAVES * 64), 0, stream,
-                         WARGS);
-      break;
-    case FN_HOLT_WINTERS:
-      hipLaunchKernelGGL((window_sample_kernel<FN_HOLT_WINTERS>),
-                         dim3((uint32_t)grid), dim3(WS_WAVES * 64), 0, stream,
-                         WARGS);
-      break;
-    case FN_DERIV:
-      hipLaunchKernelGGL((window_sample_kernel<FN_DERIV>),
-                         dim3((uint32_t)grid), dim3(WS_WAVES * 64), 0, stream,
-                         WARGS);
-      break;
+    case FN_QUANTILE:       launch(window_sample_kernel<FN_QUANTILE>); break;
+    case FN_MAD:            launch(window_sample_kernel<FN_MAD>); break;
+    case FN_PREDICT_LINEAR: launch(window_sample_kernel<FN_PREDICT_LINEAR>); break;
+    case FN_HOLT_WINTERS:   launch(window_sample_kernel<FN_HOLT_WINTERS>); break;
+    case FN_DERIV:          launch(window_sample_kernel<FN_DERIV>); break;
     default:
       fdb_set_error("window sample: unsupported func_id %d", func_id);
       return FDB_ERR_BADARG;
   }
-  #undef WARGS
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     fdb_set_error("window_sample_kernel launch failed: %s", hipGetErrorString(e));

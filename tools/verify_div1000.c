@@ -1,5 +1,5 @@
 /* Exhaustive verification of the d_div1000 Markstein sequence
- * (filodb_amd/csrc/scan_common.h): for EVERY integer |x| <= 2^33,
+ * (filodb_amd/csrc/window_funcs.h): for EVERY integer |x| <= 2^33,
  *   q0 = RN(x * r), e = fma(-1000, q0, x), q = RN(fma(e, r, q0))
  * with r = RN(1/1000) equals the correctly rounded RN(x/1000).
  * The engine's callers pass integer millisecond differences bounded by the
