@@ -1,32 +1,40 @@
-// Histogram scan v2: two-cursor monotonic walk over the sect-delta streams.
+// Histogram scan: two-cursor monotonic walk over sect-delta histogram vectors.
 //
-// Round 1 streamed every element once, holding per-bucket window-start values
-// in a ring of active windows — which capped window/step at 22 and chunks at
-// 4, and serialized on the per-element header parse (43.7 ms for the
-// BASELINE config #4 workload; profiles/README.md). v2 removes the ring:
+// One wave per series, lane l = bucket l (nb <= 64). rate(hist[w]) needs only
+// the FIRST element >= wStart and the LAST element <= wEnd of each window
+// (HistogramRateFunctionBase, RateFunctions.scala:330-400), and windows come in
+// time order, so two cursors only move forward: S tracks the window-start
+// element, E the window-end element. Each holds its chunk's timestamps in LDS
+// and hops elements by their u16 length prefix. Chunks per series, window/step
+// and num_windows are unbounded; rows per chunk <= FDB_DEFAULT_MAX_ROWS (the
+// LDS timestamp buffers; upload enforces it).
 //
-//   rate(hist[w]) per window needs only the FIRST element >= wStart and the
-//   LAST element <= wEnd (HistogramRateFunctionBase, RateFunctions.scala:
-//   330-400). Windows are processed in order by ONE wave per series with two
-//   monotone cursors — S tracks the window-start element, E the window-end
-//   element. A cursor hops elements by their u16 length prefix and fully
-//   decodes an element only when it stops on it (or at section bases, since
-//   sect-delta diffs are against the section's first element —
-//   HistogramVector.scala:491-545) — so the dependent header-parse chain runs
-//   ~twice per element worst case, with the two cursors' chains independent
-//   and overlapping, at far higher occupancy (no 12 KB ring in LDS).
+// Stage. A cursor reads its stream (section headers, length prefixes,
+// NibblePack groups) from a 256-B register window (nibble_stream.h) and keeps
+// the load of the NEXT 256 B in flight: the stream is consumed forward, so the
+// usual restage is a register swap whose wait overlapped the last two or three
+// elements' work. A cold load happens at a chunk open and when the bytes wanted
+// straddle the window's end. An element > 242 B parses from global memory.
 //
-// Unbounded: chunks per series, window/step ratio, num_windows. Per-chunk
-// rows <= 400 (the per-cursor LDS timestamp buffer; the reference's own
-// chunk cap). Corrections: TypeDrop sections add apply(e-1) per bucket
-// (Section.scala:17-24 type byte); chunk-boundary drops use
-// Histogram.compare's top-bucket-down order (Histogram.scala:204-214) —
-// same rules and per-window correction base as v1 (parity-green).
+// Decode. An element's value is the bucket-wise prefix sum of its deltas, plus
+// its section's first element unless it is that element (HistogramVector.scala:
+// 491-545). A cursor decodes section bases as it passes them, the element it
+// stops on once a window needs it (both cursors' together), and the elements
+// the corrections read. SumOverTime (SumOverTimeChunkedFunctionH: raw bucket
+// sums, no corrections) decodes every element and carries a running prefix.
+//
+// Corrections (rate). A TypeDrop section (Section.scala:17-24 type byte) adds
+// the value of the element before it, apply(e-1). At a chunk seam the previous
+// chunk's last value is added when the new chunk's first value is lower in
+// Histogram.compare's top-bucket-down order (Histogram.scala:204-214). A window
+// counts corrections from the entry of its start element's chunk: the
+// reference's per-window CorrectionMeta starts NoCorrection there.
 
 #include <cstring>
 #include <cmath>
 
 #include "engine_internal.h"
+#include "nibble_stream.h"
 
 #define H2_WAVES 4
 
@@ -45,9 +53,8 @@ __device__ __forceinline__ int64_t wave_incl_scan_i64(int64_t x, int lane) {
 // The _buf form takes a pre-staged 256-B register window so two elements'
 // stage loads can be issued together and their parse chains interleaved.
 template <bool EST>
-__device__ __forceinline__ int64_t h2_parse_est(const uint8_t* ep, int elen,
-                                                int nb, int b, bool live,
-                                                int lane, uint32_t ebuf,
+__device__ __forceinline__ int64_t h2_parse_est(const uint8_t* ep, int nb, int b,
+                                                bool live, uint32_t ebuf,
                                                 int eshift) {
   // 8-value group headers, walked serially (wave-uniform). EST is a
   // compile-time constant: with it true the walk is pure readlane + scalar
@@ -59,33 +66,18 @@ __device__ __forceinline__ int64_t h2_parse_est(const uint8_t* ep, int elen,
   uint32_t gMask = 0;
   for (int g = 0; g * 8 < nb; g++) {
     uint32_t mask = estream_byte_uni(EST, ebuf, eshift, ep, 2 + off);
-    int numBits = 0, trail = 0, glen;
-    if (mask == 0) {
-      glen = 1;
-    } else {
-      int widths = (int)estream_byte_uni(EST, ebuf, eshift, ep, 2 + off + 1);
-      numBits = ((widths >> 4) + 1) * 4;
-      trail = (widths & 0x0f) * 4;
-      glen = 2 + (numBits * __popc(mask) + 7) / 8;
-    }
-    if (g == my_group) { gOff = off; gBits = numBits; gTrail = trail; gMask = mask; }
-    off += glen;
+    const NibbleGroup grp = nibble_group(
+        mask, mask ? estream_byte_uni(EST, ebuf, eshift, ep, 2 + off + 1) : 0);
+    if (g == my_group) { gOff = off; gBits = grp.numBits; gTrail = grp.trail; gMask = mask; }
+    off += grp.glen;
   }
-  const int bit = b & 7;
-  const uint32_t in_mask = gMask & (1u << bit);
-  int slot = __popc(gMask & ((1u << bit) - 1));
-  int bitpos = slot * gBits;
-  int koff = 2 + gOff + 2 + (bitpos >> 3);
-  uint64_t w64 = estream_w64(EST, ebuf, eshift, ep, koff);
-  uint32_t b8 = estream_byte(EST, ebuf, eshift, ep, koff + 8);
+  const int k = b & 7;
+  const int bit = nibble_slot_bit(gMask, gBits, k);
+  const int koff = 2 + gOff + 2 + (bit >> 3);
+  const uint64_t w64 = estream_w64(EST, ebuf, eshift, ep, koff);
+  const uint32_t b8 = estream_byte(EST, ebuf, eshift, ep, koff + 8);
   int64_t delta = 0;
-  if (live && in_mask) {
-    int sh = bitpos & 7;
-    uint64_t v = w64 >> sh;
-    if (gBits > 64 - sh) v |= (uint64_t)b8 << (64 - sh);
-    uint64_t m = gBits >= 64 ? ~0ULL : ((1ULL << gBits) - 1);
-    delta = (int64_t)((v & m) << gTrail);
-  }
+  if (live) delta = (int64_t)nibble_slot_value(gMask, gBits, gTrail, k, bit, w64, b8);
   return delta;
 }
 
@@ -93,18 +85,10 @@ __device__ __forceinline__ int64_t h2_parse_est(const uint8_t* ep, int elen,
 // unstaged global-load path; everything else stays on the scalarized walk
 __device__ __forceinline__ int64_t h2_parse_buf(const uint8_t* ep, int elen,
                                                 int nb, int b, bool live,
-                                                int lane, uint32_t ebuf,
-                                                int eshift) {
+                                                uint32_t ebuf, int eshift) {
   if (elen + 14 + eshift <= 256)
-    return h2_parse_est<true>(ep, elen, nb, b, live, lane, ebuf, eshift);
-  return h2_parse_est<false>(ep, elen, nb, b, live, lane, ebuf, eshift);
-}
-
-__device__ __forceinline__ int64_t h2_parse(const uint8_t* ep, int elen,
-                                            int nb, int b, bool live,
-                                            int lane) {
-  return h2_parse_buf(ep, elen, nb, b, live, lane, estream_stage(ep, lane),
-                      (int)((uintptr_t)ep & 3));
+    return h2_parse_est<true>(ep, nb, b, live, ebuf, eshift);
+  return h2_parse_est<false>(ep, nb, b, live, ebuf, eshift);
 }
 
 struct H2Cursor {
@@ -127,6 +111,14 @@ struct H2Cursor {
   double prevlast_b;     // raw value of the previous chunk's last element
   double psum_b;         // per-lane running value prefix (HFUNC==1)
 };
+
+// value = section base + the deltas' bucket-wise prefix sum (scan); a section
+// base element's value is the scan of its own deltas
+__device__ __forceinline__ void h2_set_value(H2Cursor& cu, int64_t scan) {
+  if (cu.sect_first) { cu.val_b = (double)scan; cu.base_b = cu.val_b; }
+  else cu.val_b = cu.base_b + (double)scan;
+  cu.decoded = true;
+}
 
 // HFUNC 0 = counter-corrected rate (HistRateFunction); 1 = SumOverTime of
 // the histograms (raw bucket sums — SumOverTimeChunkedFunctionH, no
@@ -157,7 +149,7 @@ void hist2_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
   const int b = lane;
   const bool live = b < nb;
   const bool tmg = (abl & 8) != 0;   // s_memtime phase split into out_cnt[0..3]
-  uint64_t tAdv = 0, tDec = 0, tEmit = 0, tOther = 0, tc = 0;
+  uint64_t tAdv = 0, tDec = 0, tEmit = 0, tc = 0;
 
   for (int sid = blockIdx.x * H2_WAVES + wave; sid < num_series;
        sid += gridDim.x * H2_WAVES) {
@@ -230,12 +222,10 @@ void hist2_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
       if (cu.decoded) return;
       if (abl & 2) { cu.decoded = true; cu.val_b = 0; cu.base_b = 0; return; }
       const int off = ensure_stage(cu, cu.ep, min(cu.elen + 14, 256));
-      int64_t delta = h2_parse_buf(cu.ep, cu.elen, nb, b, live, lane,
+      int64_t delta = h2_parse_buf(cu.ep, cu.elen, nb, b, live,
                                    cu.sbuf, off);
       int64_t scan = wave_incl_scan_i64(live ? delta : 0, lane);
-      if (cu.sect_first) { cu.val_b = (double)scan; cu.base_b = cu.val_b; }
-      else cu.val_b = cu.base_b + (double)scan;
-      cu.decoded = true;
+      h2_set_value(cu, scan);
       if (HFUNC == 1) cu.psum_b += cu.val_b;   // value prefix through current
     };
 
@@ -305,7 +295,7 @@ void hist2_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
     if (!step(S, tsS_all[wave])) continue;
     open_chunk(E, 0, tsE_all[wave]);
     step(E, tsE_all[wave]);
-    bool s_more = true, e_more = true;
+    bool s_more = true;
 
     for (int w = 0; w < num_windows; w++) {
       if (tmg) tc = __builtin_amdgcn_s_memtime();
@@ -318,14 +308,13 @@ void hist2_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
         else if (E.c + 1 < nchunks) nxt = dir.start_time[first + E.c + 1];
         else break;
         if (nxt > wEnd) break;
-        if (!step(E, tsE_all[wave])) { e_more = false; break; }
+        if (!step(E, tsE_all[wave])) break;
       }
       // S → first element with ts >= wStart
       while (s_more && tsS_all[wave][S.e_local] < wStart) {
         if (!step(S, tsS_all[wave])) { s_more = false; break; }
       }
       if (tmg) { uint64_t t2m = __builtin_amdgcn_s_memtime(); tAdv += t2m - tc; tc = t2m; }
-      (void)e_more;
       if (!s_more) break;                     // no element >= wStart: done
       const int64_t t1 = tsS_all[wave][S.e_local];
       const int64_t t2 = tsE_all[wave][E.e_local];
@@ -344,17 +333,13 @@ void hist2_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
           const int lo = (c2 == S.c) ? S.e_local : 0;
           const int hi = (c2 == E.c) ? E.e_local : dir.num_rows[first + c2] - 1;
           for (int i = lo + lane; i <= hi; i += 64) {
-            double mx = d_dv_at(&xv, i);
-            double mn = d_dv_at(&nv, i);
-            if (!isnan(mx) && (isnan(wmax) || mx > wmax)) wmax = mx;
-            if (!isnan(mn) && (isnan(wmin) || mn < wmin)) wmin = mn;
+            d_fold_mm<false>(wmax, d_dv_at(&xv, i));
+            d_fold_mm<true>(wmin, d_dv_at(&nv, i));
           }
         }
         for (int off = 32; off > 0; off >>= 1) {
-          double o = __shfl_down(wmax, off);
-          if (!isnan(o) && (isnan(wmax) || o > wmax)) wmax = o;
-          o = __shfl_down(wmin, off);
-          if (!isnan(o) && (isnan(wmin) || o < wmin)) wmin = o;
+          d_fold_mm<false>(wmax, __shfl_down(wmax, off));
+          d_fold_mm<true>(wmin, __shfl_down(wmin, off));
         }
         if (lane == 0) {
           if (out_max && !isnan(wmax)) atomic_min_max_f64(&out_max[cell], wmax, false);
@@ -369,17 +354,14 @@ void hist2_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
         if (!S.decoded && !E.decoded && !(abl & 2)) {
           const int offS = ensure_stage(S, S.ep, min(S.elen + 14, 256));
           const int offE = ensure_stage(E, E.ep, min(E.elen + 14, 256));
-          int64_t dS = h2_parse_buf(S.ep, S.elen, nb, b, live, lane, S.sbuf,
+          int64_t dS = h2_parse_buf(S.ep, S.elen, nb, b, live, S.sbuf,
                                     offS);
-          int64_t dE = h2_parse_buf(E.ep, E.elen, nb, b, live, lane, E.sbuf,
+          int64_t dE = h2_parse_buf(E.ep, E.elen, nb, b, live, E.sbuf,
                                     offE);
           int64_t sS = wave_incl_scan_i64(live ? dS : 0, lane);
           int64_t sE = wave_incl_scan_i64(live ? dE : 0, lane);
-          if (S.sect_first) { S.val_b = (double)sS; S.base_b = S.val_b; }
-          else S.val_b = S.base_b + (double)sS;
-          if (E.sect_first) { E.val_b = (double)sE; E.base_b = E.val_b; }
-          else E.val_b = E.base_b + (double)sE;
-          S.decoded = true; E.decoded = true;
+          h2_set_value(S, sS);
+          h2_set_value(E, sE);
         }
         decode_cur(S);
         decode_cur(E);
@@ -413,7 +395,6 @@ void hist2_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
     atomicAdd(&out_cnt[0], (double)tAdv);
     atomicAdd(&out_cnt[1], (double)tDec);
     atomicAdd(&out_cnt[2], (double)tEmit);
-    atomicAdd(&out_cnt[3], (double)tOther);
   }
 }
 
@@ -432,19 +413,15 @@ int32_t fdb_launch_hist2(hipStream_t stream, const uint8_t* blob, DirSoA dir,
   if (cap > 0 && grid > cap) grid = cap;
   const char* hw = getenv("FDB_HIST_WAVES");   // occupancy experiment knob
   const bool w4 = hw && atoi(hw) == 4;         // 5 waves/SIMD measured best
-  const char* ab = getenv("FDB_HIST_ABLATE");  // 1=skip emits, 2=skip decodes
+  const char* ab = getenv("FDB_HIST_ABLATE");  // 1=skip emits, 2=skip decodes, 8=phase split
   const int abl = ab ? atoi(ab) : 0;
-  #define H2ARGS blob, dir, max_off, min_off, series_first, series_nchunks,       group_ids, num_series, qstart, qstep, qwindow, num_windows, nb,       out_sums, out_cnt, out_max, out_min, abl
-  if (hfunc == 1)
-    hipLaunchKernelGGL((hist2_kernel<4, 1>), dim3(grid), dim3(H2_WAVES * 64), 0,
-                       stream, H2ARGS);
-  else if (w4)
-    hipLaunchKernelGGL((hist2_kernel<4, 0>), dim3(grid), dim3(H2_WAVES * 64), 0,
-                       stream, H2ARGS);
-  else
-    hipLaunchKernelGGL((hist2_kernel<5, 0>), dim3(grid), dim3(H2_WAVES * 64), 0,
-                       stream, H2ARGS);
-  #undef H2ARGS
+  const auto kernel = hfunc == 1 ? hist2_kernel<4, 1>
+                      : w4       ? hist2_kernel<4, 0>
+                                 : hist2_kernel<5, 0>;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(H2_WAVES * 64), 0, stream,
+                     blob, dir, max_off, min_off, series_first, series_nchunks,
+                     group_ids, num_series, qstart, qstep, qwindow, num_windows,
+                     nb, out_sums, out_cnt, out_max, out_min, abl);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     fdb_set_error("hist2_kernel launch failed: %s", hipGetErrorString(e));

@@ -17,6 +17,7 @@
 #include <cstring>
 
 #include "engine_internal.h"
+#include "nibble_stream.h"
 
 __device__ __forceinline__ uint64_t wave_incl_xor(uint64_t x, int lane) {
   for (int off = 1; off < 64; off <<= 1) {
@@ -47,80 +48,39 @@ void xor_unpack_kernel(const uint8_t* __restrict__ blob,
     if (lane == 0) memcpy(&o[0], &carry, 8);
     int pos = 8, i = 1;
     while (i < n) {
-      // header walk for up to 8 groups (wave-uniform; staged 256 B)
+      // header walk for up to 8 groups (wave-uniform; staged 256 B). Whatever
+      // the two header bytes hold, the widths nibble caps numBits at 64 and popc
+      // caps the count at 8, so a group is at most 2 + 64 B: the first one
+      // always fits under the 244-B limit and ngroups >= 1, corrupt input too.
       const uint8_t* gp = p + pos;
       uint32_t stg = estream_stage(gp, lane);
       const int shift = (int)((uintptr_t)gp & 3);
-      int goff[8] = {0}, gbits[8] = {0}, gtrail[8] = {0};
-      uint32_t gmask[8] = {0};
-      int off = 0;
-      int ngroups = 0;
-      for (int g = 0; g < 8 && i + ngroups * 8 < n + 7; g++) {
-        uint32_t mask = estream_byte_uni(true, stg, shift, gp, off);
-        int numBits = 0, trail = 0, glen;
-        if (mask == 0) {
-          glen = 1;
-        } else {
-          int widths = (int)estream_byte_uni(true, stg, shift, gp, off + 1);
-          numBits = ((widths >> 4) + 1) * 4;
-          trail = (widths & 0x0f) * 4;
-          glen = 2 + (numBits * __popc(mask) + 7) / 8;
-        }
-        if (off + glen > 244) break;   // k+8+shift stays under the 64-dword stage
-        goff[g] = off; gbits[g] = numBits; gtrail[g] = trail; gmask[g] = mask;
-        off += glen;
+      // lane = (group, slot): each lane keeps its own group's header; a lane
+      // whose group the walk did not reach keeps mask 0 and extracts 0
+      NibbleGroup mine{0, 0, 0, 0};
+      int mine_off = 0, off = 0, ngroups = 0;
+      for (int g = 0; g < 8; g++) {
+        const uint32_t mask = estream_byte_uni(true, stg, shift, gp, off);
+        const NibbleGroup grp = nibble_group(
+            mask, mask ? estream_byte_uni(true, stg, shift, gp, off + 1) : 0);
+        if (off + grp.glen > 244) break;   // k+8+shift stays under the 64-dword stage
+        if (g == lane >> 3) { mine = grp; mine_off = off; }
+        off += grp.glen;
         ngroups++;
         if (i + ngroups * 8 >= n) break;      // enough values decoded
       }
-      if (ngroups == 0) {                     // giant group: bounce via lane 0
-        uint32_t mask = estream_byte(true, stg, shift, gp, 0);
-        int widths = (int)estream_byte(true, stg, shift, gp, 1);
-        int numBits = ((widths >> 4) + 1) * 4;
-        int trail = (widths & 0x0f) * 4;
-        int glen = 2 + (numBits * __popc(mask) + 7) / 8;
-        int k = lane & 7;
-        uint64_t delta = 0;
-        if ((lane >> 3) == 0 && (mask & (1u << k))) {
-          int slot = __popc(mask & ((1u << k) - 1));
-          int bitpos = slot * numBits;
-          uint64_t w;
-          memcpy(&w, gp + 2 + (bitpos >> 3), 8);
-          w >>= (bitpos & 7);
-          if (numBits > 64 - (bitpos & 7)) {
-            uint64_t hi = gp[2 + (bitpos >> 3) + 8];
-            w |= hi << (64 - (bitpos & 7));
-          }
-          uint64_t m = numBits >= 64 ? ~0ULL : ((1ULL << numBits) - 1);
-          delta = (w & m) << trail;
-        }
-        uint64_t chain = wave_incl_xor(lane < 8 ? delta : 0, lane) ^ carry;
-        if (lane < 8 && i + lane < n) memcpy(&o[i + lane], &chain, 8);
-        int take = n - i < 8 ? n - i : 8;
-        carry = __shfl(chain, take - 1 < 7 ? take - 1 : 7);
-        i += take;
-        pos += glen;
-        continue;
-      }
-      // lane = (group, slot): extract this lane's delta. The estream reads
-      // are SHUFFLES, so every lane must execute them (inactive source lanes
-      // yield undefined data) — only the final delta is predicated.
-      const int g = lane >> 3, k = lane & 7;
-      const bool lvalid = g < ngroups && (gmask[g] & (1u << k));
-      int slot = lvalid ? __popc(gmask[g] & ((1u << k) - 1)) : 0;
-      int bitpos = slot * gbits[g];
-      int koff = goff[g] + 2 + (bitpos >> 3);
-      uint64_t w = estream_w64(true, stg, shift, gp, koff);
-      uint32_t b8 = estream_byte(true, stg, shift, gp, koff + 8);
-      uint64_t delta = 0;
-      if (lvalid) {
-        int sh = bitpos & 7;
-        uint64_t v = w >> sh;
-        if (gbits[g] > 64 - sh) v |= (uint64_t)b8 << (64 - sh);
-        uint64_t m = gbits[g] >= 64 ? ~0ULL : ((1ULL << gbits[g]) - 1);
-        delta = (v & m) << gtrail[g];
-      }
+      // The estream reads are SHUFFLES, so every lane must execute them
+      // (inactive source lanes yield undefined data): only the value is
+      // predicated, on the mask bit.
+      const int k = lane & 7;
+      const int bit = nibble_slot_bit(mine.mask, mine.numBits, k);
+      const int koff = mine_off + 2 + (bit >> 3);
+      const uint64_t w = estream_w64(true, stg, shift, gp, koff);
+      const uint32_t b8 = estream_byte(true, stg, shift, gp, koff + 8);
+      const uint64_t delta = nibble_slot_value(mine.mask, mine.numBits, mine.trail,
+                                               k, bit, w, b8);
       // prefix-XOR reconstructs up to 64 chain values at once
-      uint64_t chain = wave_incl_xor(g < ngroups ? delta : 0, lane) ^ carry;
+      uint64_t chain = wave_incl_xor(delta, lane) ^ carry;
       const int avail = ngroups * 8;
       const int take = (n - i) < avail ? (n - i) : avail;
       if (lane < take) memcpy(&o[i + lane], &chain, 8);
@@ -128,11 +88,9 @@ void xor_unpack_kernel(const uint8_t* __restrict__ blob,
       i += take;
       pos += off;
     }
-    d_wait_lds();
-    __builtin_amdgcn_wave_barrier();
+    d_lds_fence();
   }
 }
-
 
 // host entry: decodes num_streams packed streams (host memory) on the GPU.
 // offs/counts/out_offs are host arrays; out is a host buffer.

@@ -383,66 +383,4 @@ __device__ inline void atomic_min_max_f64(double* addr, double val, bool is_min)
   } while (old != assumed);
 }
 
-// --- wave-staged element stream -------------------------------------------
-// One coalesced dword-per-lane load stages 256 B of an element's NibblePack
-// stream into the wave's registers; all subsequent byte/u16/u64 reads are
-// register shuffles (ds_bpermute) instead of dependent global loads. The
-// stage for element e+1 is issued before element e is parsed, so the load
-// latency overlaps a full element's parse work. Elements longer than the
-// staged range (elen+shift > 252, i.e. huge sections) fall back to direct
-// global reads; the blob is tail-padded 256 B at upload so staging never
-// faults.
-__device__ __forceinline__ uint32_t estream_stage(const uint8_t* p, int lane) {
-  const uint8_t* base = (const uint8_t*)((uintptr_t)p & ~(uintptr_t)3);
-  uint32_t d;
-  memcpy(&d, base + lane * 4, 4);
-  return d;
-}
-// `staged` must be WAVE-UNIFORM and every call site must have the full wave
-// active: __shfl is ds_bpermute, and a source lane that is inactive (or a
-// divergent caller) yields undefined data.
-__device__ __forceinline__ uint32_t estream_byte(bool staged, uint32_t buf,
-                                                 int shift, const uint8_t* g,
-                                                 int k) {
-  if (staged) {
-    int kk = k + shift;
-    uint32_t d = __shfl(buf, kk >> 2);
-    return (d >> ((kk & 3) * 8)) & 0xff;
-  }
-  return g[k];
-}
-// wave-UNIFORM byte read from the staged window: kk>>2 is the same for every
-// lane, so v_readlane (scalar result, no LDS pipe) replaces ds_bpermute —
-// the header walks of the NibblePack parsers are built from these
-__device__ __forceinline__ uint32_t estream_byte_uni(bool staged, uint32_t buf,
-                                                     int shift, const uint8_t* g,
-                                                     int k) {
-  if (staged) {
-    int kk = k + shift;
-    uint32_t d = __builtin_amdgcn_readlane(buf, kk >> 2);
-    return (d >> ((kk & 3) * 8)) & 0xff;
-  }
-  return g[k];
-}
-
-// little-endian 8-byte window at offset k (per-lane k; bpermute shuffles)
-__device__ __forceinline__ uint64_t estream_w64(bool staged, uint32_t buf,
-                                                int shift, const uint8_t* g,
-                                                int k) {
-  if (staged) {
-    int kk = k + shift;
-    int dw = kk >> 2;
-    uint64_t a = __shfl(buf, dw);
-    uint64_t b = __shfl(buf, dw + 1);
-    uint64_t c = __shfl(buf, dw + 2);
-    int sh = (kk & 3) * 8;
-    uint64_t w = (a | (b << 32)) >> sh;
-    if (sh) w |= c << (64 - sh);
-    return w;
-  }
-  uint64_t w;
-  memcpy(&w, g + k, 8);
-  return w;
-}
-
 #endif  // FDB_SCAN_COMMON_H
