@@ -38,7 +38,10 @@
 //    the LDS footprint and read traffic; chunk span is checked at upload)
 //  * the extrapolatedRate epilogue keeps the oracle's exact operation
 //    sequence (its threshold comparisons are discontinuous — see
-//    fast_window_value); AVG/STDDEV use a per-block reciprocal table
+//    fast_window_value), in the core's lean form: bit-identical, with the
+//    avgDur division through a per-block reciprocal table and the v1/delta
+//    division branched around where it provably decides nothing
+//    (rate_core.h); AVG/STDDEV use a per-block reciprocal table of their own
 //    (continuous, ≤2 ulp)
 //  * window results are branch-lean selects; one store per window
 //
@@ -138,15 +141,21 @@ __device__ __forceinline__ FDesc fast_load_desc(const FdbFastDesc* desc, int s) 
   return FDesc{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w}};
 }
 
-// reciprocal table users (AVG/STDDEV/STDVAR; the rate epilogue keeps the
-// oracle's exact divisions, see fast_window_value)
+// reciprocal table users: AVG/STDDEV/STDVAR index it by a sample count up to
+// the row cap; the rate epilogue's lean core by numSamples-1 below
+// FDB_RATE_RTAB, exactly (rate_core.h). 256 entries put the K_RATE block at
+// 22,720 B of LDS, inside the 23,405 B that 7 blocks/CU leave each.
 template <int KIND> constexpr bool needs_inv = KIND == K_PFX || KIND == K_PFX_SQ;
+template <int KIND> constexpr int inv_entries =
+    needs_inv<KIND> ? FDB_DEFAULT_MAX_ROWS + 2 : KIND == K_RATE ? FDB_RATE_RTAB : 0;
 
 // wave-uniform constants of the query
 struct FastQuery {
   int64_t qstep, qwindow;
   double rate_scale, dur_ms;     // 1000/qwindow, (double)qwindow
   bool qw32;                     // the window fits i32: i32 rate epilogue
+  int rk_lim;                    // lean rate core: table entries usable at this
+                                 // window length (0: it divides)
 };
 
 // TIMED: the s_memtime phase split (perf ablation: tools/perf_sweep.py sets
@@ -335,9 +344,15 @@ struct FastBounds {
     const int32_t tlast = n > 0 ? tso[n - 1] : 0;
     lin.last = __builtin_amdgcn_readfirstlane(tlast);
     lin.inv_h = (n >= 2 && lin.last > 0) ? (float)(n - 1) / (float)lin.last : 0.0f;
+    // the seed: slot -1's start rows. Where the series begins after window
+    // -1 ends (wave-uniform; any series or chunk that starts inside the
+    // queried range) every one of those searches finds no row, e = -1 and
+    // s = 0: s_prev stays 0 and the fifth search is not run.
     if constexpr (SHARE) {
-      int32_t unused;
-      end_search(lane - 64, &unused, &s_prev);
+      if (!fdb_windows_before_chunk(-1, q.qstep, Ae)) {
+        int32_t unused;
+        end_search(lane - 64, &unused, &s_prev);
+      }
     }
   }
   __device__ __forceinline__ WB window_bounds(int w) const {
@@ -416,9 +431,10 @@ __device__ __forceinline__ double fast_window_value(const WS& ws, const WB& wb, 
         }
         const int64_t wEndOff = (int64_t)w * q.qstep - Ae;   // wEnd - ts0
         if (q.qw32)    // uniform: window fits i32 ⇒ so do all three gaps
-          res = d_extrapolated_rate_i32(
+          res = d_extrapolated_rate_i32<true>(
               (int32_t)(t1 - (wEndOff - q.qwindow)), (int32_t)(wEndOff - t2),
-              e - s + 1, t2 - t1, q.dur_ms, v1, v2, IS_COUNTER, FUNC == FN_RATE);
+              e - s + 1, t2 - t1, q.dur_ms, v1, v2, IS_COUNTER, FUNC == FN_RATE,
+              inv_tab, q.rk_lim);
         else
           res = d_extrapolated_rate(wEndOff - q.qwindow, wEndOff, e - s + 1,
                                     t1, v1, t2, v2, IS_COUNTER, FUNC == FN_RATE);
@@ -534,7 +550,8 @@ struct FastGroupAcc {
 
 // MINW = min waves/SIMD the register allocator must meet. PFX_SQ is
 // LDS-bound at 4 blocks/CU; the group-emit variant carries 12 accumulator
-// registers (4 waves); K_RATE (no reciprocal table, LDS fits 7 blocks/CU) is
+// registers (4 waves); K_RATE (a 256-entry reciprocal table: 22,720 B of LDS
+// per block, which still fits 7 blocks/CU) is
 // built at 7 as measured on hardware (profiles/README.md, rounds 3 and 4);
 // the gauge kinds are built at 6. Since round 5 the bounds no longer bind:
 // with the decoders' lane-scaled blob addresses kept out of the series loop's
@@ -558,7 +575,7 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob,
 {
   constexpr int KIND = FKind<FUNC>::v;
   __shared__ FWs<KIND> ws_all[FAST_WAVES];
-  __shared__ double inv_tab[needs_inv<KIND> ? FDB_DEFAULT_MAX_ROWS + 2 : 1];
+  __shared__ double inv_tab[inv_entries<KIND> ? inv_entries<KIND> : 1];
 
   // readfirstlane pins the wave id (and everything derived from it — series
   // ids, descriptor addresses) as wave-uniform for the compiler: the whole
@@ -568,14 +585,15 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob,
   const int lane = threadIdx.x & 63;
   FWs<KIND>& ws = ws_all[wave];
 
-  if (needs_inv<KIND>) {
-    for (int i = threadIdx.x; i < FDB_DEFAULT_MAX_ROWS + 2; i += FAST_WAVES * 64)
+  if (inv_entries<KIND>) {
+    for (int i = threadIdx.x; i < inv_entries<KIND>; i += FAST_WAVES * 64)
       inv_tab[i] = 1.0 / (double)i;          // [0] = +inf (never a divisor)
     __syncthreads();
   }
 
   const FastQuery q{qstep, qwindow, 1000.0 / (double)qwindow, (double)qwindow,
-                    qwindow < ((int64_t)1 << 31)};
+                    qwindow < ((int64_t)1 << 31),
+                    qwindow <= (int64_t)FDB_RATE_RTAB_MAX_MS ? FDB_RATE_RTAB : 0};
   FastTimer<TIMED> timer;
 
   // series iteration: grid-stride for the plain grid emit; a contiguous slab
@@ -618,8 +636,9 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob,
     for (int tb = 0; tb < num_windows; tb += FAST_TILE) {
       const int tn = min(FAST_TILE, num_windows - tb);
       // the timed variant computes all four windows' bounds ahead of the
-      // window phase so the split can charge them to PH_BOUNDS; the sink
-      // keeps them alive although its result stores are suppressed
+      // window phase so the split can charge them to PH_BOUNDS; the sinks
+      // keep them, and each window's result, alive although its result
+      // stores are suppressed
       WB tbnd[TIMED ? 4 : 1];
       if constexpr (TIMED) {
         #pragma unroll
@@ -642,6 +661,7 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob,
         if constexpr (TIMED) wb = tbnd[k];
         else wb = bnd.calc_bounds(k, w, wok, tn);
         const double res = fast_window_value<FUNC>(ws, wb, w, ch, rs, bnd.Ae, q, inv_tab);
+        if constexpr (TIMED) asm volatile("" :: "v"(res));
         if (EMIT == 1) acc.accumulate(k, agg_id, res);
         else if (wok && !TIMED) out[(size_t)sid * num_windows + w] = res;
       }

@@ -157,4 +157,14 @@ FDB_HD inline int fdb_bound_s_from_e(const int32_t* tso, int n, FdbLin lin,
   return s;
 }
 
+// True when every window up to index w_last (wEnd(w) = qstart + w*qstep,
+// qstep > 0, Ae = ts0 - qstart) ends before the chunk's first row: its end
+// offset w_last*qstep - Ae is negative and tso[0] >= 0, so for each of them
+// e = -1 and the start row at that offset is 0, with no search. The fast scan
+// kernel's shared search asks this for its seed slot (w_last = -1).
+FDB_HD inline bool fdb_windows_before_chunk(int64_t w_last, int64_t qstep,
+                                            int64_t Ae) {
+  return w_last * qstep - Ae < 0;
+}
+
 #endif  // FDB_WINDOW_BOUNDS_H

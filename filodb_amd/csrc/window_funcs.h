@@ -8,41 +8,7 @@
 #define FDB_WINDOW_FUNCS_H
 
 #include "scan_common.h"
-
-// Correctly-rounded x/1000 in 3 ops (mul + 2 fma, Markstein fixup) instead of
-// the ~10-instruction v_div_scale/v_div_fmas/v_div_fixup sequence. EXACTLY
-// equal to RN(x/1000) for every integer |x| <= 2^33 — verified exhaustively
-// (8.59e9 cases, 0 mismatches; the naive q0 = x*(1/1000) alone differs on 13%
-// of them). Callers pass integer millisecond DIFFERENCES bounded by the
-// window length; the engine rejects windows > 2^33 ms (~99 days) up front.
-__device__ __forceinline__ double d_div1000(double x) {
-  constexpr double r = 1.0 / 1000.0;                // RN reciprocal
-  double q0 = x * r;
-  double e = __builtin_fma(-1000.0, q0, x);         // exact residual
-  return __builtin_fma(e, r, q0);
-}
-
-// extrapolatedRate (RateFunctions.scala:72-111) from the three durations in
-// seconds to scaledDelta — the oracle's EXACT operation sequence. Do not
-// reassociate or replace the divisions: the durationToZero/threshold
-// comparisons are discontinuous and integer counter data makes exact rational
-// ties (v1/delta == 1.1/(numSamples-1)) common, so the branch taken must
-// follow the reference's own FP rounding.
-__device__ __forceinline__ double d_extrapolate_core(
-    double durationToStart, double durationToEnd, double sampledInterval,
-    int numSamples, double v1, double v2, bool isCounter) {
-  double avgDur = sampledInterval / ((double)numSamples - 1);
-  double delta = v2 - v1;
-  if (isCounter && delta > 0 && v1 >= 0) {
-    double durationToZero = sampledInterval * (v1 / delta);
-    if (durationToZero < durationToStart) durationToStart = durationToZero;
-  }
-  double thresh = avgDur * 1.1;
-  double ext = sampledInterval;
-  ext += (durationToStart < thresh) ? durationToStart : avgDur / 2;
-  ext += (durationToEnd < thresh) ? durationToEnd : avgDur / 2;
-  return delta * (ext / sampledInterval);
-}
+#include "rate_core.h"   // d_div1000, d_extrapolate_core
 
 // i64 timestamps (the walk, hist2). The /1000 sites use d_div1000 —
 // bit-identical on the engine's ms-difference domain.
@@ -59,13 +25,17 @@ __device__ inline double d_extrapolated_rate(
 // i32 when the window does (caller checks), so each i64 subtract +
 // 4-instruction i64→f64 convert becomes a truncate + single v_cvt_f64_i32; the
 // window duration is wave-uniform and passed pre-converted. Same values into
-// the same core, so results are bit-identical to d_extrapolated_rate.
+// the same core, so results are bit-identical to d_extrapolated_rate. LEAN
+// selects the core's lean form (rate_core.h: same bits, two divisions fewer
+// where provable) with the reciprocal table rk[0..rk_lim).
+template <bool LEAN = false>
 __device__ inline double d_extrapolated_rate_i32(
     int32_t toStart_ms, int32_t toEnd_ms, int numSamples, int32_t sampled_ms,
-    double dur_ms, double v1, double v2, bool isCounter, bool isRate) {
-  double scaledDelta = d_extrapolate_core(
+    double dur_ms, double v1, double v2, bool isCounter, bool isRate,
+    const double* rk = nullptr, int rk_lim = 0) {
+  double scaledDelta = d_extrapolate_core<LEAN>(
       d_div1000((double)toStart_ms), d_div1000((double)toEnd_ms),
-      d_div1000((double)sampled_ms), numSamples, v1, v2, isCounter);
+      d_div1000((double)sampled_ms), numSamples, v1, v2, isCounter, rk, rk_lim);
   return isRate ? (scaledDelta / dur_ms * 1000.0) : scaledDelta;
 }
 
