@@ -60,6 +60,11 @@ struct fdb_dataset {
   // upload when fast_ok; fast_desc_sc describes the count column riding
   // max_off (has_sc) so avg_sc's second scan takes the same kernel
   FdbFastDesc *fast_desc, *fast_desc_sc;
+  // host copies of up to FDB_FAST_SAMPLE evenly spaced descriptors per table:
+  // the launcher runs the aligned-rows test on them with the query at hand
+  // and picks the kernel build by the share that passes (scan_fast.hip)
+  FdbFastDesc fast_sample[2][FDB_FAST_SAMPLE];
+  int fast_nsample;
 };
 
 // the dataset's chunk directory as the kernels take it; count_col swaps the
@@ -254,6 +259,9 @@ extern "C" fdb_dataset_t* fdb_dataset_upload(fdb_engine_t* e, const fdb_store_t*
                             has ? nr[c] : 0, &desc[(size_t)sid]);
       }
       if (!addressable) { d->fast_ok = 0; break; }
+      d->fast_nsample = ns < FDB_FAST_SAMPLE ? ns : FDB_FAST_SAMPLE;
+      for (int k = 0; k < d->fast_nsample; k++)
+        d->fast_sample[col][k] = desc[(size_t)((int64_t)k * ns / d->fast_nsample)];
       ok = upload((void**)(col ? &d->fast_desc_sc : &d->fast_desc), desc.data(),
                   desc.size() * sizeof(FdbFastDesc));
       if (!ok) break;
@@ -299,6 +307,7 @@ static int32_t launch_scan(fdb_engine_t* e, const fdb_dataset_t* d, const fdb_qu
   if (fast_eligible(d, q) && q->agg_id == AGG_NONE) {
     return fdb_launch_fast_scan(e->stream, d->blob,
                                 count_col ? d->fast_desc_sc : d->fast_desc,
+                                d->fast_sample[count_col ? 1 : 0], d->fast_nsample,
                                 d->group_ids,
                                 d->series_by_group, d->num_series,
                                 q->start, q->step, q->window, nw,
@@ -439,7 +448,7 @@ static int32_t run_query(fdb_engine_t* e, const fdb_dataset_t* d, const fdb_quer
       if (dev_sq && !(needs_sq && partial))
         HIP_CHECK(hipMemsetAsync(dev_sq.get(), 0, out_len * 8, e->stream));
       return fdb_launch_fast_scan(
-          e->stream, d->blob, d->fast_desc,
+          e->stream, d->blob, d->fast_desc, d->fast_sample[0], d->fast_nsample,
           d->group_ids, d->series_by_group, d->num_series,
           q->start, q->step, q->window, nw, q->func_id, q->agg_id,
           /*emit_group=*/1, dev_out.get(), dev_cnt.get(), dev_sq.get(), q->_pad);

@@ -92,8 +92,10 @@ inline bool fdb_scan_supported(int func_id) {
 
 // scan_fast.hip: single-chunk-per-series fast path
 struct FdbFastDesc;   // fast_desc.h: one decode descriptor per series
+#define FDB_FAST_SAMPLE 256   // host-side descriptor sample kept per dataset
 int32_t fdb_launch_fast_scan(hipStream_t stream, const uint8_t* blob,
                              const FdbFastDesc* desc,
+                             const FdbFastDesc* sample, int nsample,   // host
                              const int32_t* group_ids, const int32_t* series_by_group,
                              int num_series,
                              int64_t qstart, int64_t qstep, int64_t qwindow,

@@ -9,6 +9,14 @@
 // series holds the parsed result, so the kernel fetches it with one scalar
 // load through a wave-uniform address and goes straight to the payload.
 //
+// ts_rmin / ts_rmax bound the timestamp vector's residuals: inner[i] of a
+// packed vector over the series' rows, 0 for a const one. With them the
+// kernel decides, in scalar arithmetic and without touching a row, whether
+// every row sits within one query step of "its" window edge, and then takes
+// each window's rows directly (window_bounds.h, fdb_aligned_*). ts_rmin >
+// ts_rmax marks a series that never qualifies: raw 64-bit timestamps, no
+// rows, residuals outside i16, or offsets that leave i32.
+//
 // Host-only, plain C++ (no HIP): engine.hip builds the table,
 // tools/verify_fast_desc.cpp checks the builder against a restatement of the
 // device header parser and a lane-by-lane model of the decode.
@@ -39,7 +47,8 @@ struct FdbFastDesc {
   int32_t  ts_slope;
   int64_t  val_init;
   int32_t  val_slope;
-  uint32_t _pad[5];
+  int16_t  ts_rmin, ts_rmax;   // min / max timestamp residual; rmin > rmax: none
+  uint32_t _pad[4];
 };
 static_assert(sizeof(FdbFastDesc) == 64, "one 64-byte scalar load per series");
 
@@ -119,6 +128,7 @@ inline void fdb_build_fast_desc(const uint8_t* blob, uint64_t ts_off,
                                 FdbFastDesc* out) {
   FdbFastDesc d;
   memset(&d, 0, sizeof(d));
+  d.ts_rmin = 1;             // rmin > rmax: not eligible for direct window rows
   if (num_rows > 0) {
     const FdbFdVec tv = fdb_fd_open(blob + ts_off);
     const FdbFdVec vv = fdb_fd_open(blob + val_off);
@@ -134,6 +144,28 @@ inline void fdb_build_fast_desc(const uint8_t* blob, uint64_t ts_off,
       d.n = (uint16_t)num_rows;
       d.ts0 = tv.first;
       d.ts_base = (int32_t)(tv.init - tv.first);
+      // residual range of the timestamp vector: tso[i] = ts_base + ts_slope*i
+      // + inner[i] must hold in plain integers (no i32 wrap) for the
+      // aligned-window test to stand on it
+      if (tv.cls != FDB_FD_RAW64 &&
+          tv.init - tv.first >= INT32_MIN && tv.init - tv.first <= INT32_MAX) {
+        const uint8_t* idata = blob + ts_off + tv.payload;
+        const bool sg = (tv.flags & FDB_FD_SIGN) != 0;
+        int64_t rmin = 0, rmax = 0;
+        bool fits = true;
+        for (int i = 0; i < num_rows && fits; i++) {
+          const int64_t in = tv.cls == FDB_FD_PACKED
+                                 ? fdb_fd_inner(idata, tv.nbits, sg, i) : 0;
+          const int64_t off = (tv.init - tv.first) + (int64_t)tv.slope * i + in;
+          if (i == 0 || in < rmin) rmin = in;
+          if (i == 0 || in > rmax) rmax = in;
+          fits = off >= 0 && off <= INT32_MAX;
+        }
+        if (fits && rmin >= INT16_MIN && rmax <= INT16_MAX) {
+          d.ts_rmin = (int16_t)rmin;
+          d.ts_rmax = (int16_t)rmax;
+        }
+      }
       if (vv.cls == FDB_FD_PACKED && vv.n >= num_rows &&
           vv.init > -((int64_t)1 << 52) && vv.init < ((int64_t)1 << 52)) {
         const uint8_t* idata = blob + val_off + vv.payload;

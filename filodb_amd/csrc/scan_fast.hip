@@ -8,9 +8,9 @@
 //    and both vector headers are parsed on the host into one 64-byte record
 //    per series — payload offsets, row count (row guards already decided),
 //    wire-format class / nbits / sign, drop bit, ts0, timestamp base and
-//    slope, value init and slope, val_exact32. The kernel loads desc[sid]
-//    through a wave-uniform address and goes straight to the payload: two
-//    dependent memory trips per series instead of the four of
+//    slope and residual range, value init and slope, val_exact32. The kernel
+//    loads desc[sid] through a wave-uniform address and goes straight to the
+//    payload: two dependent memory trips per series instead of the four of
 //    series_first -> directory row -> 32-B headers -> payload
 //  * packed 8/16-bit delta-delta vectors decode four rows per lane (one
 //    payload load, 128-bit LDS stores, no per-row guard; scan_common.h), the
@@ -34,6 +34,22 @@
 //    the edge) and travels to the lane that owns window w+m through one
 //    ds_bpermute — five searches per lane and tile instead of eight, no LDS
 //    array. Any other window/step pair keeps two searches per window.
+//  * where, in a SHARE build, the step also matches the series' scrape grid —
+//    every row within one step of "its" window edge (window_bounds.h,
+//    condition C; the commonest dashboard shape and the benchmark's) — there
+//    is nothing to search: window w's end row is row w-k0 or the one before,
+//    its start row is row w-m-k0 or the one after, one comparison each on two
+//    neighbouring cells read together. The series is chosen per wave, in
+//    scalar arithmetic, from the residual range the descriptor carries
+//    (ts_rmin / ts_rmax, fast_desc.h), without touching a row; an aligned
+//    series skips the last-row read, the slope divide, the seed search and
+//    the exchange. Everything else — raw timestamp vectors, dropped scrapes,
+//    another interval — keeps the search, series by series within one
+//    launch. Holding both paths costs the searched series registers, so the
+//    ALIGNED build is a template parameter picked per launch, where a host-
+//    side sample of the descriptors says at least a quarter of the series
+//    qualify under the query at hand; every other launch, and FDB_ALIGNED=0
+//    (read at launch), takes the search-only build.
 //  * timestamps live in LDS as i32 offsets from the chunk's first ts (halves
 //    the LDS footprint and read traffic; chunk span is checked at upload)
 //  * the extrapolatedRate epilogue keeps the oracle's exact operation
@@ -91,8 +107,13 @@ template <int KIND>
 struct alignas(16) FWs {            // per-wave LDS workspace; tso[] and val[]
                                     // start 16-B aligned and hold a multiple of
                                     // four rows (128-bit decode stores)
-  int32_t tso[FDB_DEFAULT_MAX_ROWS + 4];   // ts - ts0 (i32 offsets); the pad keeps
-                                           // tso[startRow] readable at startRow == n
+  // ts - ts0 (i32 offsets) in one array: four cells of front pad keep
+  // tso()[-1] readable (the aligned end bound reads tso[j-1], tso[j] at j >= 0;
+  // the value is never used) and tso() 16-B aligned; the back pad keeps
+  // tso()[startRow] readable at startRow == n
+  int32_t tsbuf[4 + FDB_DEFAULT_MAX_ROWS + 4];
+  __device__ __forceinline__ int32_t* tso() { return tsbuf + 4; }
+  __device__ __forceinline__ const int32_t* tso() const { return tsbuf + 4; }
   double  val[FDB_DEFAULT_MAX_ROWS];       // raw values, or prefix sums (PFX kinds)
   uint16_t cnt[(KIND == K_PFX || KIND == K_PFX_SQ || KIND == K_CHANGES)
                    ? FDB_DEFAULT_MAX_ROWS : 1];
@@ -122,10 +143,13 @@ struct FDesc {
   __device__ __forceinline__ int64_t val_init() const {
     return (int64_t)(((uint64_t)w[9] << 32) | w[8]); }
   __device__ __forceinline__ int32_t val_slope() const { return (int32_t)w[10]; }
+  __device__ __forceinline__ int32_t ts_rmin() const { return (int32_t)(int16_t)(w[11] & 0xffff); }
+  __device__ __forceinline__ int32_t ts_rmax() const { return (int32_t)w[11] >> 16; }
 };
 static_assert(offsetof(FdbFastDesc, n) == 8 && offsetof(FdbFastDesc, ts_flags) == 12 &&
               offsetof(FdbFastDesc, ts0) == 16 && offsetof(FdbFastDesc, ts_base) == 24 &&
-              offsetof(FdbFastDesc, val_init) == 32 && offsetof(FdbFastDesc, val_slope) == 40,
+              offsetof(FdbFastDesc, val_init) == 32 && offsetof(FdbFastDesc, val_slope) == 40 &&
+              offsetof(FdbFastDesc, ts_rmin) == 44 && offsetof(FdbFastDesc, ts_rmax) == 46,
               "FDesc's dword views follow FdbFastDesc's layout");
 
 // series bookkeeping: one 64-B descriptor per series (fast_desc.h), parsed
@@ -144,7 +168,7 @@ __device__ __forceinline__ FDesc fast_load_desc(const FdbFastDesc* desc, int s) 
 // reciprocal table users: AVG/STDDEV/STDVAR index it by a sample count up to
 // the row cap; the rate epilogue's lean core by numSamples-1 below
 // FDB_RATE_RTAB, exactly (rate_core.h). 256 entries put the K_RATE block at
-// 22,720 B of LDS, inside the 23,405 B that 7 blocks/CU leave each.
+// 22,784 B of LDS, inside the 23,405 B that 7 blocks/CU leave each.
 template <int KIND> constexpr bool needs_inv = KIND == K_PFX || KIND == K_PFX_SQ;
 template <int KIND> constexpr int inv_entries =
     needs_inv<KIND> ? FDB_DEFAULT_MAX_ROWS + 2 : KIND == K_RATE ? FDB_RATE_RTAB : 0;
@@ -156,6 +180,7 @@ struct FastQuery {
   bool qw32;                     // the window fits i32: i32 rate epilogue
   int rk_lim;                    // lean rate core: table entries usable at this
                                  // window length (0: it divides)
+  float inv_qstep;               // steers the aligned path's k0 estimate
 };
 
 // TIMED: the s_memtime phase split (perf ablation: tools/perf_sweep.py sets
@@ -189,8 +214,9 @@ template <bool TIMED> struct FastTimer {
 // n..4*ceil(n/4)-1 of tso[] and val[] hold garbage. Nothing interprets them:
 // the meta loops guard i < n, the bound search accepts rows < n only
 // (window_bounds.h reads past n but never interprets it), every window row
-// range keeps s <= e < n, and the one tso[s] read at s == n (shared_bounds)
-// is readable and never used.
+// range keeps s <= e < n, and the one tso[s] read at s == n (shared_bounds;
+// the aligned start bound's tso[j+1] at j == n-1) is readable and never used,
+// like tso[-1] (FWs::tsbuf's front pad, the aligned end bound at j == 0).
 struct FastChunk { int n; int64_t ts0; bool dropped; };
 
 template <typename WS>
@@ -217,7 +243,7 @@ __device__ __forceinline__ FastChunk fast_decode(const FDesc& cd, const uint8_t*
     tv.slope = cd.ts_slope();
     tv.n = n; tv.nbits = (uint8_t)cd.ts_nbits();
     tv.sign = (cd.ts_flags() & FDB_FD_SIGN) != 0; tv.dropped = 0;
-    d_decode_ts_offsets(tv, n, ts0, ws.tso, dl);
+    d_decode_ts_offsets(tv, n, ts0, ws.tso(), dl);
     const int vcls = cd.val_cls(), vbits = cd.val_nbits();
     const bool vsign = (cd.val_flags() & FDB_FD_SIGN) != 0;
     const bool exact32 = (cd.val_flags() & FDB_FD_EXACT32) != 0;
@@ -326,7 +352,13 @@ struct WB { int s, e; int32_t t1, t2; };
 // ds_bpermute delivers, and only the previous slot's start row stays live.
 // Five searches per lane instead of eight: four ends plus the seed for the
 // windows before the first tile.
-template <bool SHARE>
+//
+// ALIGNED (a SHARE build that also holds the direct rows; chosen per launch,
+// fdb_launch_fast_scan): each series is tested against condition C and takes
+// the direct rows or the search. The plain SHARE build holds the search
+// alone, so a launch the direct rows would not serve keeps that build's
+// registers and instruction text.
+template <bool SHARE, bool ALIGNED>
 struct FastBounds {
   const int32_t* tso;
   int n, lane, wshare;
@@ -337,10 +369,25 @@ struct FastBounds {
   int s_prev;         // start row at the end of this lane's window in the
                       // previous slot; slot -1 = windows -64..-1
 
+  FdbAligned al;      // ALIGNED: the series takes the direct rows (wave-uniform)
+
+  // nw: windows of the launch
   __device__ __forceinline__ FastBounds(const int32_t* tso_, int n_, int64_t Ae_,
-                                        const FastQuery& q_, int wshare_, int lane_)
-      : tso(tso_), n(n_), lane(lane_), wshare(wshare_), q(q_), Ae(Ae_),
-        share_src(((lane_ - wshare_) & 63) << 2), s_prev(0) {
+                                        const FastQuery& q_, int wshare_, int lane_,
+                                        const FDesc& cd, int nw)
+      : tso(tso_), n(n_), lane(lane_), wshare(wshare_), q(q_), lin{0, 0.0f}, Ae(Ae_),
+        share_src(((lane_ - wshare_) & 63) << 2), s_prev(0), al{false, 0, 0} {
+    // the step matches this series' scrape grid (window_bounds.h, condition
+    // C, decided from the descriptor in scalar arithmetic): each window's rows
+    // come from one comparison, and the last-row read, the divide, the seed
+    // search and the exchange below are all skipped
+    if constexpr (ALIGNED) {
+      const int32_t k0 = __builtin_amdgcn_readfirstlane(fdb_aligned_guess(
+          cd.ts_base(), cd.ts_rmin(), cd.ts_rmax(), Ae, q.inv_qstep));
+      al = fdb_aligned_test(n, cd.ts_base(), cd.ts_slope(), cd.ts_rmin(),
+                            cd.ts_rmax(), Ae, q.qstep, wshare, nw, k0);
+      if (al.ok) return;
+    }
     const int32_t tlast = n > 0 ? tso[n - 1] : 0;
     lin.last = __builtin_amdgcn_readfirstlane(tlast);
     lin.inv_h = (n >= 2 && lin.last > 0) ? (float)(n - 1) / (float)lin.last : 0.0f;
@@ -379,6 +426,15 @@ struct FastBounds {
     b.t1 = tso[b.s];     // 0 <= s <= n; tso[n] is readable, never used
     return b;
   }
+  // the direct rows of an aligned series: i32 throughout (fdb_aligned_test
+  // checked the launch's offsets), no state, no other lane involved
+  __device__ __forceinline__ WB aligned_bounds(int w) const {
+    WB b;
+    const int32_t x = (int32_t)((uint32_t)al.x0 + (uint32_t)w * (uint32_t)q.qstep);
+    const int32_t y = (int32_t)((uint32_t)x - (uint32_t)q.qwindow);
+    fdb_aligned_bounds(tso, n, al.k0, w, wshare, x, y, &b.e, &b.s, &b.t1, &b.t2);
+    return b;
+  }
   // slot k's bounds in a tile of tn windows; slots run in order k = 0..3 (the
   // shared search hands slot k-1 on to slot k, and slot 3 on to the next
   // tile's slot 0). A window that is not there (!wok) gets the empty range
@@ -388,7 +444,9 @@ struct FastBounds {
     WB b = WB{1, -1, 0, 0};
     if constexpr (SHARE) {
       if (64 * k < tn) {             // wave-uniform: the slot has windows
-        const WB sb = shared_bounds(w);
+        WB sb;
+        if (ALIGNED && al.ok) sb = aligned_bounds(w);
+        else sb = shared_bounds(w);
         if (wok) b = sb;
       }
     } else if (wok) {
@@ -492,7 +550,7 @@ __device__ __forceinline__ double fast_window_value(const WS& ws, const WB& wb, 
     if (e > s) {
       const double last = ws.val[e], prev = ws.val[e - 1];
       if constexpr (FUNC == FN_IDELTA) res = last - prev;
-      else res = d_irate_finish(last, prev, (double)(wb.t2 - ws.tso[e - 1]));
+      else res = d_irate_finish(last, prev, (double)(wb.t2 - ws.tso()[e - 1]));
     }
   } else {  // FN_ZSCORE
     if (e >= s && e >= 0) {
@@ -550,7 +608,7 @@ struct FastGroupAcc {
 
 // MINW = min waves/SIMD the register allocator must meet. PFX_SQ is
 // LDS-bound at 4 blocks/CU; the group-emit variant carries 12 accumulator
-// registers (4 waves); K_RATE (a 256-entry reciprocal table: 22,720 B of LDS
+// registers (4 waves); K_RATE (a 256-entry reciprocal table: 22,784 B of LDS
 // per block, which still fits 7 blocks/CU) is
 // built at 7 as measured on hardware (profiles/README.md, rounds 3 and 4);
 // the gauge kinds are built at 6. Since round 5 the bounds no longer bind:
@@ -559,7 +617,8 @@ struct FastGroupAcc {
 // VGPRs with no scratch (FN_RATE 53, FN_AVG 44), and occupancy is set by LDS
 // alone. SHARE selects the shared window search (window = 1..64 whole steps;
 // wshare carries that ratio): a template parameter, not a runtime branch.
-template <int FUNC, int EMIT, int MINW, bool TIMED = false, bool SHARE = false>
+template <int FUNC, int EMIT, int MINW, bool TIMED = false, bool SHARE = false,
+          bool ALIGNED = false>
 __global__ __launch_bounds__(FAST_WAVES * 64, MINW)
 void fast_scan_kernel(const uint8_t* __restrict__ blob,
                       const FdbFastDesc* __restrict__ desc,
@@ -593,7 +652,8 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob,
 
   const FastQuery q{qstep, qwindow, 1000.0 / (double)qwindow, (double)qwindow,
                     qwindow < ((int64_t)1 << 31),
-                    qwindow <= (int64_t)FDB_RATE_RTAB_MAX_MS ? FDB_RATE_RTAB : 0};
+                    qwindow <= (int64_t)FDB_RATE_RTAB_MAX_MS ? FDB_RATE_RTAB : 0,
+                    1.0f / (float)qstep};
   FastTimer<TIMED> timer;
 
   // series iteration: grid-stride for the plain grid emit; a contiguous slab
@@ -632,7 +692,8 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob,
       acc.cur_grp = group_ids[sid];
     }
 
-    FastBounds<SHARE> bnd(ws.tso, ch.n, ch.ts0 - qstart, q, wshare, lane);
+    FastBounds<SHARE, ALIGNED> bnd(ws.tso(), ch.n, ch.ts0 - qstart, q, wshare, lane,
+                                   cd, num_windows);
     for (int tb = 0; tb < num_windows; tb += FAST_TILE) {
       const int tn = min(FAST_TILE, num_windows - tb);
       // the timed variant computes all four windows' bounds ahead of the
@@ -682,6 +743,7 @@ struct FastLaunch {   // grid, stream, the kernel's arguments, the build selecto
   int num_series; int64_t qstart, qstep, qwindow; int num_windows, agg_id;
   double *out, *out_cnt, *out_sq;
   int wshare;         // 0: two searches per window
+  bool aligned;       // shared search only: the build that holds the direct rows
   bool emit_group, timed;
 };
 
@@ -691,8 +753,10 @@ struct FastLaunch {   // grid, stream, the kernel's arguments, the build selecto
 // shapes; elsewhere the bit changes nothing.
 template <int F, int EMIT, int MINW, bool TIMED>
 static void launch_fast_as(const FastLaunch& a) {
-  const auto kernel = a.wshare ? fast_scan_kernel<F, EMIT, MINW, TIMED, true>
-                               : fast_scan_kernel<F, EMIT, MINW, TIMED, false>;
+  const auto kernel =
+      !a.wshare ? fast_scan_kernel<F, EMIT, MINW, TIMED, false, false>
+      : a.aligned ? fast_scan_kernel<F, EMIT, MINW, TIMED, true, true>
+                  : fast_scan_kernel<F, EMIT, MINW, TIMED, true, false>;
   hipLaunchKernelGGL(kernel, dim3(a.grid), dim3(FAST_WAVES * 64), 0, a.stream,
                      a.blob, a.desc, a.group_ids, a.sbg, a.num_series, a.qstart,
                      a.qstep, a.qwindow, a.num_windows, a.agg_id, a.out, a.out_cnt,
@@ -706,8 +770,14 @@ static void launch_fast(const FastLaunch& a) {
   launch_fast_as<F, 0, MINW, false>(a);
 }
 
+// test hook: how many descriptors of the sample passed the aligned-rows test
+// at the last launch if that launch took the ALIGNED build, else 0
+static int32_t g_last_aligned = 0;
+extern "C" int32_t fdb_debug_last_fast_aligned(void) { return g_last_aligned; }
+
 int32_t fdb_launch_fast_scan(hipStream_t stream, const uint8_t* blob,
                              const FdbFastDesc* desc,
+                             const FdbFastDesc* sample, int nsample,
                              const int32_t* group_ids, const int32_t* series_by_group,
                              int num_series,
                              int64_t qstart, int64_t qstep, int64_t qwindow,
@@ -725,9 +795,33 @@ int32_t fdb_launch_fast_scan(hipStream_t stream, const uint8_t* blob,
       qwindow / qstep <= 64)
     wshare = (int)(qwindow / qstep);
   if (const char* s = getenv("FDB_WINDOW_SHARE")) { if (atoi(s) == 0) wshare = 0; }
+  // The build that also holds the direct rows (ALIGNED) costs a series that
+  // does not qualify about 2 % (registers, SGPR spills: profiles/README.md,
+  // round 7) and saves one that does about 9 %, so it is launched only where
+  // at least a quarter of the dataset qualifies under THIS query: the
+  // kernel's own test, run here on the host-side descriptor sample kept at
+  // upload. Any other launch keeps the search-only build.
+  // (FDB_ALIGNED=0: always the search-only build, for A/B runs)
+  int sampled = 0, eligible = 0;
+  if (wshare) {
+    const float inv_q = 1.0f / (float)qstep;
+    for (int i = 0; i < nsample; i++) {
+      const FdbFastDesc& d = sample[i];
+      if (d.n == 0) continue;
+      sampled++;
+      const int64_t A = d.ts0 - qstart;
+      const int32_t k0 = fdb_aligned_guess(d.ts_base, d.ts_rmin, d.ts_rmax, A, inv_q);
+      if (fdb_aligned_test(d.n, d.ts_base, d.ts_slope, d.ts_rmin, d.ts_rmax, A, qstep,
+                           wshare, num_windows, k0).ok)
+        eligible++;
+    }
+  }
+  bool aligned = eligible > 0 && 4 * eligible >= sampled;
+  if (const char* s = getenv("FDB_ALIGNED")) { if (atoi(s) == 0) aligned = false; }
+  g_last_aligned = aligned ? eligible : 0;
   const FastLaunch a{grid, stream, blob, desc, group_ids, series_by_group,
                      num_series, qstart, qstep, qwindow, num_windows, agg_id,
-                     out, out_cnt, out_sq, wshare, emit_group != 0,
+                     out, out_cnt, out_sq, wshare, aligned, emit_group != 0,
                      (phase_mask & 8) != 0};   // bit 3: s_memtime phase ablation
   switch (func_id) {     // <function, plain-grid MINW>
     case FN_RATE:            launch_fast<FN_RATE, 7>(a); break;   // LDS: 7 blocks/CU

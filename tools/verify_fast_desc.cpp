@@ -15,7 +15,8 @@
 // random vectors and a bench-law sample (fdb_synth_generate, the law of
 // bench.py's rate_1m). For every series:
 //  * "fields": fdb_build_fast_desc against open_ref below, a literal
-//    restatement of the device's d_vec_open_wide, field for field;
+//    restatement of the device's d_vec_open_wide, field for field, and the
+//    timestamp residual range (ts_rmin / ts_rmax) against the element reader;
 //  * "rows": a lane-by-lane replay of the kernel's decode (64 lanes, 256-row
 //    passes, whole 4-row groups stored with no per-row guard) into sentinel-
 //    filled tso[404] / val[400]; every row < n must equal the element
@@ -24,7 +25,8 @@
 //    its vector's end ("overread", max over all lanes) must stay <= 6 and
 //    inside the blob plus its 512-B upload pad.
 // One line per store: "store=<name> series=<n> fields=<n> rows=<n>
-// exact32=<n> overread=<bytes> mismatches=<n>".
+// exact32=<n> resid=<n> overread=<bytes> mismatches=<n>" (resid: series with a
+// valid timestamp residual range, ts_rmin <= ts_rmax).
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -204,7 +206,7 @@ void decode_val4(Span& sp, const uint8_t* idata, bool sign, int64_t init,
     }
 }
 
-struct Totals { long series = 0, fields = 0, rows = 0, exact32 = 0, mism = 0; int over = 0; };
+struct Totals { long series = 0, fields = 0, rows = 0, exact32 = 0, resid = 0, mism = 0; int over = 0; };
 
 const int32_t kSentT = 0x5a5a5a5a;
 const double kSentV = -7.25e300;
@@ -222,7 +224,11 @@ void check_series(const fdb_view_t& view, int32_t sid, Totals& t) {
     if (t.mism < 10) fprintf(stderr, "series %d: %s\n", sid, what);
     t.mism++;
   };
-  if (!has) { if (d.n != 0) bad("n of an empty series"); return; }
+  if (!has) {
+    if (d.n != 0) bad("n of an empty series");
+    if (d.ts_rmin <= d.ts_rmax) bad("ts_rmin/ts_rmax of an empty series");
+    return;
+  }
   const RefVec tv = open_ref(blob + e->ts_off), vv = open_ref(blob + e->val_off);
   // ---- fields ----
   int n = e->num_rows;
@@ -254,6 +260,26 @@ void check_series(const fdb_view_t& view, int32_t sid, Totals& t) {
       ex = off >= INT32_MIN && off <= INT32_MAX;
     }
     FIELD(((d.val_flags & FDB_FD_EXACT32) != 0) == ex, "val_exact32");
+    // ts_rmin / ts_rmax restated from the element reader: the residuals
+    // lv_at(i) - (init + slope*i) over the rows, valid only where every
+    // offset from the first timestamp is a non-negative i32 and both bounds
+    // fit i16; never for a raw vector
+    bool rok = tv.wf != FDB_WF_PRIM64 &&
+               tv.init - tv.first >= INT32_MIN && tv.init - tv.first <= INT32_MAX;
+    int64_t rmin = 0, rmax = 0;
+    for (int i = 0; rok && i < n; i++) {
+      const int64_t off = lv_at(tv, i) - tv.first;
+      const int64_t res = lv_at(tv, i) - (tv.init + (int64_t)tv.slope * i);
+      if (i == 0 || res < rmin) rmin = res;
+      if (i == 0 || res > rmax) rmax = res;
+      rok = off >= 0 && off <= INT32_MAX;
+    }
+    rok = rok && rmin >= INT16_MIN && rmax <= INT16_MAX;
+    FIELD(rok ? (d.ts_rmin == rmin && d.ts_rmax == rmax) : d.ts_rmin > d.ts_rmax,
+          "ts_rmin/ts_rmax");
+    if (rok) t.resid++;
+  } else {
+    FIELD(d.ts_rmin > d.ts_rmax, "ts_rmin/ts_rmax of an empty series");
   }
 #undef FIELD
   if (d.val_flags & FDB_FD_EXACT32) t.exact32++;
@@ -348,8 +374,9 @@ int report(const char* name, fdb_store_t* st, long* exact_out = nullptr) {
   if (fdb_store_view(st, &view) != FDB_OK) { fprintf(stderr, "%s: no view\n", name); return 1; }
   Totals t;
   for (int32_t sid = 0; sid < view.num_series; sid++) check_series(view, sid, t);
-  printf("store=%s series=%ld fields=%ld rows=%ld exact32=%ld overread=%d mismatches=%ld\n",
-         name, t.series, t.fields, t.rows, t.exact32, t.over, t.mism);
+  printf("store=%s series=%ld fields=%ld rows=%ld exact32=%ld resid=%ld overread=%d "
+         "mismatches=%ld\n", name, t.series, t.fields, t.rows, t.exact32, t.resid, t.over,
+         t.mism);
   if (exact_out) *exact_out = t.exact32;
   fdb_store_destroy(st);
   return (t.mism != 0 || t.over > 6) ? 1 : 0;
