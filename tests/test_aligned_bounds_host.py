@@ -9,14 +9,12 @@ slow drift, duplicate timestamps inside the condition, row counts 1..8,
 series and a scrape interval that is not the step check that the test never
 accepts a series the condition does not hold for. No GPU, nothing loaded into
 Python (hipcc only supplies the include path of the store's source file)."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from verifier_run import STORE_SRC, run_verifier
+
 CLASSES = ["bench", "zerojitter", "driftm1", "driftp1", "driftm5", "driftp5",
            "dups", "widejitter", "drop", "irregular", "interval10s", "benchlaw"]
 FIELDS = ("cases", "eligible", "c_holds", "rejected_c", "windows", "mismatches")
@@ -27,29 +25,17 @@ ALIGNED = ["bench", "zerojitter", "driftm1", "driftp1", "driftm5", "driftp5"]
 
 @pytest.fixture(scope="module")
 def report(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or os.path.join(
-        os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
-    assert os.path.exists(hipcc), "no hipcc"
-    exe = str(tmp_path_factory.mktemp("ab") / "verify_aligned_bounds")
-    subprocess.run([hipcc, "-O2", "-std=c++17", "-fopenmp", "-o", exe,
-                    os.path.join(REPO, "tools", "verify_aligned_bounds.cpp"),
-                    os.path.join(REPO, "filodb_amd", "csrc", "chunk_builder.cpp")],
-                   check=True)
-    p = subprocess.run([exe], capture_output=True, text=True)
-    print(p.stdout)
-    print(p.stderr)
-    rows = {}
-    pat = r"class=(\w+) " + " ".join(f + r"=(\d+)" for f in FIELDS)
-    for m in re.finditer(pat, p.stdout):
-        rows[m.group(1)] = dict(zip(FIELDS, map(int, m.groups()[1:])))
-    bench = re.search(r"bench-law series eligible: (\d+) of (\d+)", p.stdout)
-    return p.returncode, rows, bench
+    rc, out, rows = run_verifier("verify_aligned_bounds", tmp_path_factory.mktemp("ab"),
+                                 flags=["-fopenmp"], sources=[STORE_SRC])
+    bench = re.search(r"bench-law series eligible: (\d+) of (\d+)", out)
+    return rc, rows, bench
 
 
 def test_direct_bounds_match_linear_scan(report):
     rc, rows, _ = report
     assert sorted(rows) == sorted(CLASSES)
     for cls, r in rows.items():
+        assert tuple(r) == FIELDS, cls
         assert r["mismatches"] == 0, cls
         assert r["eligible"] <= r["c_holds"], cls     # never accepted without C
     for cls in ALIGNED:

@@ -33,10 +33,9 @@ direct against searched is checked bit for bit. The oracle comparison is left
 out for this one class: the stored last row then precedes the chunk's recorded
 end time, and engine and oracle disagree on timestamp() for a window that
 starts in between, on the search path as much as on the direct one."""
-import numpy as np
 import pytest
 
-from conftest import build_store
+import window_cases as wc
 
 pytestmark = pytest.mark.gpu
 
@@ -55,57 +54,8 @@ FUNCS = ["FN_RATE", "FN_INCREASE", "FN_DELTA", "FN_AVG_OVER_TIME",
 EXACT = ("FN_COUNT_OVER_TIME", "FN_TIMESTAMP")
 
 
-def _jitter(rng, n, amp):
-    """+-amp ms, with row 0 and the last row on the line and row 1 a full amp
-    off it: the builder stores a vector whose rows all lie within 250 ms of
-    that line as a const one, rounding every row onto the line, and the
-    engine and the oracle do not agree on such a chunk's last millisecond."""
-    j = rng.integers(-amp, amp + 1, n)
-    j[0] = j[-1] = 0
-    if n >= 3:
-        j[1] = amp
-    return j
-
-
-def _timestamps(cls, rng, n):
-    i = np.arange(n, dtype=np.int64)
-    if cls == "bench":
-        t = i * STEP + _jitter(rng, n, 300)
-    elif cls == "constjit":                 # stored as a const vector
-        t = i * STEP + rng.integers(-100, 101, n)
-    elif cls == "zerojitter":               # every row exactly on a window edge
-        t = i * STEP
-    elif cls.startswith("drift"):           # scrape interval q-1, q+1, q-5, q+5
-        d = {"m1": -1, "p1": 1, "m5": -5, "p5": 5}[cls[5:]]
-        t = i * (STEP + d) + (_jitter(rng, n, 300) if abs(d) == 1 else 0)
-    elif cls == "dups":
-        t = i * STEP + rng.integers(-50, 51, n)
-        for k in range(1, n - 2, 3):        # rows 0 and n-1 stay on the grid
-            t[k] = k * STEP + STEP * 11 // 20
-            t[k + 1] = t[k]
-    elif cls == "drop":                     # one scrape missing in the middle
-        t = (i + (i > n // 2)) * STEP + _jitter(rng, n, 300)
-    else:                                   # "10s": interval is not the step
-        t = i * 10_000 + _jitter(rng, n, 300)
-    return T0 + np.maximum.accumulate(t)
-
-
-class Case:
-    def __init__(self, fdb, engine, cls):
-        rng = np.random.default_rng(7000 + CLASSES.index(cls))
-        series, groups = [], []
-        for n in SIZES:
-            for law, resets in ((cls, False), (cls, True), ("drop", True),
-                                ("10s", False)):
-                ts = _timestamps(law, rng, n)
-                vals = np.cumsum(rng.poisson(10.0, n).astype(np.float64))
-                if resets:
-                    for i in np.nonzero(rng.random(n) < 0.05)[0]:
-                        vals[i:] -= vals[i]
-                series.append([[(int(t), float(v)) for t, v in zip(ts, vals)]])
-                groups.append(len(series) % 3)
-        self.store = build_store(fdb, series, kind=fdb.COL_COUNTER, groups=groups)
-        self.ds = engine.upload(self.store)
+def _timestamps(law, rng, n):
+    return wc.aligned_ts(law, rng, n, T0, STEP)
 
 
 @pytest.fixture(scope="module")
@@ -115,13 +65,11 @@ def engine(fdb):
 
 @pytest.fixture(scope="module")
 def cases(fdb, engine):
-    cache = {}
-
-    def get(cls):
-        if cls not in cache:
-            cache[cls] = Case(fdb, engine, cls)
-        return cache[cls]
-    return get
+    # four series per size: the class with and without counter resets, and
+    # two that must not take the direct path
+    return wc.case_cache(lambda cls: wc.Case(
+        fdb, engine, cls, SIZES, 7000 + CLASSES.index(cls), _timestamps,
+        plan=((cls, False), (cls, True), ("drop", True), ("10s", False))))
 
 
 def _query(fdb, nw, m, phase, func, agg=0, groups=0):
@@ -137,10 +85,7 @@ def _engine(engine, case, q, monkeypatch, aligned):
         monkeypatch.delenv("FDB_ALIGNED", raising=False)
     else:
         monkeypatch.setenv("FDB_ALIGNED", "0")
-    ns, nw = case.store.num_series, q.num_windows
-    got = np.empty((q.num_groups if q.agg_id else ns) * nw, dtype=np.float64)
-    engine.query(case.ds, q, out=got)
-    return got
+    return wc.run_engine(engine, case, q)
 
 
 @pytest.mark.parametrize("nw", NUM_WINDOWS)
@@ -148,7 +93,6 @@ def _engine(engine, case, q, monkeypatch, aligned):
 def test_direct_rows_equal_search_and_oracle(fdb, oracle, engine, cases, cls, nw,
                                              monkeypatch):
     case = cases(cls)
-    ns = case.store.num_series
     for m, phase in QUERIES:
         for name in FUNCS:
             q = _query(fdb, nw, m, phase, getattr(fdb, name))
@@ -162,12 +106,11 @@ def test_direct_rows_equal_search_and_oracle(fdb, oracle, engine, cases, cls, nw
             assert on.tobytes() == off.tobytes(), what
             if cls in NO_ORACLE:
                 continue
-            want = oracle.query_exec(case.store.view(), q, ns, nw, nthreads=4)
+            want = wc.run_oracle(oracle, case, q)
             if name in EXACT:
-                np.testing.assert_array_equal(on, want, err_msg=what)
+                wc.assert_exact(on, want, what)
             else:
-                np.testing.assert_allclose(on, want, rtol=1e-9, atol=1e-12,
-                                           equal_nan=True, err_msg=what)
+                wc.assert_close(on, want, what)
 
 
 @pytest.mark.parametrize("fused", ["0", "1"])
@@ -176,11 +119,9 @@ def test_sum_by_group(fdb, oracle, engine, cases, fused, monkeypatch):
     fused-group emit, direct path on and off."""
     monkeypatch.setenv("FDB_FUSED_GROUP", fused)
     case = cases("bench")
-    ns = case.store.num_series
     for m, phase in ((20, 0), (20, STEP - 1), (64, -1)):
         q = _query(fdb, 241, m, phase, fdb.FN_RATE, fdb.AGG_SUM, 3)
-        want = oracle.query_exec(case.store.view(), q, ns, 241, nthreads=4)
+        want = wc.run_oracle(oracle, case, q)
         for aligned in (True, False):
             got = _engine(engine, case, q, monkeypatch, aligned)
-            np.testing.assert_allclose(got, want, rtol=1e-9, atol=1e-12,
-                                       equal_nan=True)
+            wc.assert_close(got, want)

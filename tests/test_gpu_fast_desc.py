@@ -34,6 +34,7 @@ import struct
 import numpy as np
 import pytest
 
+import window_cases as wc
 from conftest import build_store
 
 pytestmark = pytest.mark.gpu
@@ -208,22 +209,7 @@ def engine(fdb):
 
 @pytest.fixture(scope="module")
 def cases(fdb, engine):
-    cache = {}
-
-    def get(name):
-        if name not in cache:
-            cache[name] = Case(fdb, engine, name)
-        return cache[name]
-    return get
-
-
-def _run(oracle, engine, case, q):
-    ns, nw = case.store.num_series, q.num_windows
-    out_len = (q.num_groups if q.agg_id else ns) * nw
-    want = oracle.query_exec(case.store.view(), q, ns, nw, nthreads=4)
-    got = np.empty(out_len, dtype=np.float64)
-    engine.query(case.ds, q, out=got)
-    return got, want
+    return wc.case_cache(lambda name: Case(fdb, engine, name))
 
 
 @pytest.mark.parametrize("name", TS_STORES + VAL_STORES)
@@ -235,8 +221,8 @@ def test_every_row_vs_oracle(fdb, oracle, engine, cases, name):
         for func in (FN_LAST, FN_COUNT, FN_TIMESTAMP):
             q = fdb.make_query(start, step, end, step, func)
             assert q.num_windows == nw
-            got, want = _run(oracle, engine, case, q)
-            np.testing.assert_array_equal(got, want)
+            got, want = wc.run_both(oracle, engine, case, q)
+            wc.assert_exact(got, want)
             if func == FN_COUNT:
                 seen += int(np.nansum(want))
                 if name != "t8s":       # strictly increasing rows: one per window
@@ -250,10 +236,9 @@ def test_every_row_vs_oracle(fdb, oracle, engine, cases, name):
     nw = min(nw * case.qstep // step + 1, 700)
     for func in (FN_RATE, FN_AVG):
         q = fdb.make_query(start, step, start + (nw - 1) * step, 20 * step, func)
-        got, want = _run(oracle, engine, case, q)
+        got, want = wc.run_both(oracle, engine, case, q)
         assert np.isfinite(want).any()
-        np.testing.assert_allclose(got, want, rtol=1e-9, atol=1e-12,
-                                   equal_nan=True)
+        wc.assert_close(got, want)
 
 
 def test_avg_sc_second_table(fdb, oracle, engine):
@@ -273,7 +258,7 @@ def test_avg_sc_second_table(fdb, oracle, engine):
     want = oracle.query_exec_avg_sc(st.view(), q, st.num_series, q.num_windows)
     got = engine.query_avg_sc(ds, q)
     assert np.isfinite(want).any()
-    np.testing.assert_allclose(got, want, rtol=1e-9, atol=1e-12, equal_nan=True)
+    wc.assert_close(got, want)
 
 
 def test_fused_group_sum(fdb, oracle, engine, cases, monkeypatch):
@@ -284,6 +269,5 @@ def test_fused_group_sum(fdb, oracle, engine, cases, monkeypatch):
     for func in (FN_RATE, FN_COUNT):
         q = fdb.make_query(T0, 15000, T0 + 240 * 15000, 300_000, func,
                            fdb.AGG_SUM, 3)
-        got, want = _run(oracle, engine, case, q)
-        np.testing.assert_allclose(got, want, rtol=1e-9, atol=1e-12,
-                                   equal_nan=True)
+        got, want = wc.run_both(oracle, engine, case, q)
+        wc.assert_close(got, want)

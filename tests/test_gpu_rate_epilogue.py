@@ -41,9 +41,12 @@ Stores are single-chunk, at most 64 series each:
               mid-range, interleaved: the waves of one block take both seed
               branches
 """
+from types import SimpleNamespace
+
 import numpy as np
 import pytest
 
+import window_cases as wc
 from conftest import build_store
 
 pytestmark = pytest.mark.gpu
@@ -140,48 +143,39 @@ def engine(fdb):
 
 @pytest.fixture(scope="module")
 def stores(fdb, engine):
-    cache = {}
-
-    def get(name):
-        if name not in cache:
-            series = _series(name)
-            assert 0 < len(series) <= 64
-            st = build_store(
-                fdb, [[[(int(t), float(v)) for t, v in zip(ts, vals)]]
-                      for ts, vals in series],
-                kind=fdb.COL_COUNTER, groups=[i % NGROUPS for i in range(len(series))])
-            cache[name] = (st, engine.upload(st))
-        return cache[name]
-    return get
+    def make(name):
+        series = _series(name)
+        assert 0 < len(series) <= 64
+        st = build_store(
+            fdb, [[[(int(t), float(v)) for t, v in zip(ts, vals)]]
+                  for ts, vals in series],
+            kind=fdb.COL_COUNTER, groups=[i % NGROUPS for i in range(len(series))])
+        return SimpleNamespace(store=st, ds=engine.upload(st))
+    return wc.case_cache(make)
 
 
 @pytest.mark.parametrize("name,shape", CASES)
 def test_rate_epilogue_vs_oracle(fdb, oracle, engine, stores, monkeypatch, name, shape):
-    st, ds = stores(name)
+    case = stores(name)
     off, step, nw, window = SHAPES[name][shape]
     start = T0 + off
     end = start + (nw - 1) * step
-    ns = st.num_series
     for fname, func in FUNCS.items():
         q = fdb.make_query(start, step, end, window, func)
         assert q.num_windows == nw
-        want = oracle.query_exec(st.view(), q, ns, nw, nthreads=4)
-        got = np.empty(ns * nw, dtype=np.float64)
-        engine.query(ds, q, out=got)
+        got, want = wc.run_both(oracle, engine, case, q)
         assert np.isfinite(want).sum() > 0, "the case computes nothing"
         print(f"{name}[{shape}] {fname} none: equal={np.array_equal(got, want, equal_nan=True)}")
-        np.testing.assert_array_equal(got, want)
+        wc.assert_exact(got, want)
 
         qs = fdb.make_query(start, step, end, window, func, fdb.AGG_SUM, NGROUPS)
-        want = oracle.query_exec(st.view(), qs, ns, nw, nthreads=4)
+        want = wc.run_oracle(oracle, case, qs)
         for fused in ("0", "1"):
             monkeypatch.setenv("FDB_FUSED_GROUP", fused)
-            got = np.empty(NGROUPS * nw, dtype=np.float64)
-            engine.query(ds, qs, out=got)
+            got = wc.run_engine(engine, case, qs)
             print(f"{name}[{shape}] {fname} sum fused={fused}: "
                   f"equal={np.array_equal(got, want, equal_nan=True)}")
             if (name, fused) in EXACT_SUM:
-                np.testing.assert_array_equal(got, want)
+                wc.assert_exact(got, want)
             else:
-                np.testing.assert_allclose(got, want, rtol=1e-9, atol=1e-12,
-                                           equal_nan=True)
+                wc.assert_close(got, want)

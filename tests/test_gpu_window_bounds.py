@@ -18,10 +18,9 @@ practice). Every window edge here is = 0 or 2 (mod 10) relative to T0, and
 the two duplicate classes place their rows at 5 (mod 10), so no edge lands on
 a run and the comparison stays exact; edges that hit a row exactly are
 covered by the duplicate-free "grid" and "bench" (row 0) stores."""
-import numpy as np
 import pytest
 
-from conftest import build_store
+import window_cases as wc
 
 pytestmark = pytest.mark.gpu
 
@@ -34,59 +33,9 @@ DUP_CLASSES = ("allequal", "dupruns")
 FN_RATE, FN_COUNT, FN_AVG, FN_TIMESTAMP = 0, 4, 5, 14
 
 
-def _scrape(rng, n, drop, jitter=300):
-    grid = np.arange(int(n / (1 - drop)) + 64)
-    if drop > 0:
-        grid = grid[rng.random(grid.size) >= drop]
-    grid = grid[:n]
-    assert grid.size == n
-    return grid * STEP + rng.integers(-jitter, jitter + 1, n)
-
-
 def _timestamps(cls, rng, n):
-    if cls == "bench":
-        t = _scrape(rng, n, 0.0)
-    elif cls == "grid":                     # rows exactly on wEnd and wStart
-        t = np.arange(n) * STEP
-    elif cls.startswith("drop"):
-        t = _scrape(rng, n, int(cls[4:]) / 100.0)
-    elif cls == "geometric":                # gaps double, restart every 21 rows
-        gaps = 1 << (np.arange(n) % 21)
-        t = np.concatenate([[0], np.cumsum(gaps)[:-1]])
-    elif cls == "clusters":                 # two dense clusters, one 2^30 gap
-        gaps = rng.integers(900, 1101, n)
-        if n >= 2:
-            gaps[n // 2 - 1] = 1 << 30
-        t = np.concatenate([[0], np.cumsum(gaps)[:-1]])
-    elif cls == "allequal":
-        t = np.zeros(n, dtype=np.int64)
-    else:                                   # dupruns: runs of 1..5 equal rows
-        runs = rng.integers(1, 6, n)
-        base = np.cumsum(STEP + rng.integers(-300, 301, n))
-        t = np.repeat(base, runs)[:n]
-    t = np.maximum.accumulate(np.asarray(t, dtype=np.int64))
-    t = T0 + t - t[0]
-    if cls in DUP_CLASSES:
-        t = t // 10 * 10 + 5      # off every window edge (module docstring)
-    return t
-
-
-class Case:
-    def __init__(self, fdb, engine, cls):
-        rng = np.random.default_rng(1000 + CLASSES.index(cls))
-        series, groups = [], []
-        for n in SIZES:
-            for resets in (False, True):    # rate path with and without drops
-                ts = _timestamps(cls, rng, n)
-                vals = np.cumsum(rng.poisson(10.0, n).astype(np.float64))
-                if resets:
-                    for i in np.nonzero(rng.random(n) < 0.05)[0]:
-                        vals[i:] -= vals[i]
-                series.append([[(int(t), float(v)) for t, v in zip(ts, vals)]])
-                groups.append(len(series) % 3)
-        self.max_ts = max(ch[0][-1][0] for ch in series)
-        self.store = build_store(fdb, series, kind=fdb.COL_COUNTER, groups=groups)
-        self.ds = engine.upload(self.store)
+    # the duplicate classes sit off every window edge (module docstring)
+    return wc.scrape_ts(cls, rng, n, T0, STEP, off_edges=cls in DUP_CLASSES)
 
 
 @pytest.fixture(scope="module")
@@ -96,13 +45,8 @@ def engine(fdb):
 
 @pytest.fixture(scope="module")
 def cases(fdb, engine):
-    cache = {}
-
-    def get(cls):
-        if cls not in cache:
-            cache[cls] = Case(fdb, engine, cls)
-        return cache[cls]
-    return get
+    return wc.case_cache(lambda cls: wc.Case(
+        fdb, engine, cls, SIZES, 1000 + CLASSES.index(cls), _timestamps))
 
 
 def _shape(name, case):
@@ -135,15 +79,6 @@ SHAPES = ["div", "nodiv", "sparse", "longwin", "win2p31", "wide", "before",
           "after", "nw1", "nw64", "nw65", "nw256", "nw257", "nw600"]
 
 
-def _run(fdb, oracle, engine, case, q):
-    ns, nw = case.store.num_series, q.num_windows
-    out_len = (q.num_groups if q.agg_id else ns) * nw
-    want = oracle.query_exec(case.store.view(), q, ns, nw, nthreads=4)
-    got = np.empty(out_len, dtype=np.float64)
-    engine.query(case.ds, q, out=got)
-    return got, want
-
-
 @pytest.mark.parametrize("shape", SHAPES)
 @pytest.mark.parametrize("cls", CLASSES)
 def test_bounds_vs_oracle(fdb, oracle, engine, cases, cls, shape):
@@ -153,13 +88,12 @@ def test_bounds_vs_oracle(fdb, oracle, engine, cases, cls, shape):
     for func in (FN_COUNT, FN_TIMESTAMP):       # the bounds themselves: exact
         q = fdb.make_query(start, step, end, window, func)
         assert q.num_windows == nw
-        got, want = _run(fdb, oracle, engine, case, q)
-        np.testing.assert_array_equal(got, want)
+        got, want = wc.run_both(oracle, engine, case, q)
+        wc.assert_exact(got, want)
     for func in (FN_RATE, FN_AVG):
         q = fdb.make_query(start, step, end, window, func)
-        got, want = _run(fdb, oracle, engine, case, q)
-        np.testing.assert_allclose(got, want, rtol=1e-9, atol=1e-12,
-                                   equal_nan=True)
+        got, want = wc.run_both(oracle, engine, case, q)
+        wc.assert_close(got, want)
 
 
 @pytest.mark.parametrize("cls", ["bench", "drop30", "clusters"])
@@ -170,6 +104,5 @@ def test_fused_group_sum(fdb, oracle, engine, cases, cls, monkeypatch):
     for func in (FN_RATE, FN_COUNT):
         q = fdb.make_query(T0, STEP, T0 + 240 * STEP, 300_000, func,
                            fdb.AGG_SUM, 3)
-        got, want = _run(fdb, oracle, engine, case, q)
-        np.testing.assert_allclose(got, want, rtol=1e-9, atol=1e-12,
-                                   equal_nan=True)
+        got, want = wc.run_both(oracle, engine, case, q)
+        wc.assert_close(got, want)

@@ -6,28 +6,19 @@ and fdb_windows_before_chunk against the seed search it replaces. This runs
 its reduced domain ("quick": ms <= 2^16, 2e6 core inputs, under a second);
 the full domain (1.7e10 table cases, 1.2e9 core inputs) is the tool's own
 documented run. No GPU, nothing loaded into Python."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from verifier_run import run_verifier
+
 
 
 @pytest.fixture(scope="module")
 def report(tmp_path_factory):
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    exe = str(tmp_path_factory.mktemp("re") / "verify_rate_epilogue")
-    subprocess.run([cxx, "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe,
-                    os.path.join(REPO, "tools", "verify_rate_epilogue.cpp")],
-                   check=True)
-    p = subprocess.run([exe, "quick"], capture_output=True, text=True)
-    print(p.stdout)
-    print(p.stderr)
-    return p.returncode, p.stdout
+    rc, out, _ = run_verifier("verify_rate_epilogue", tmp_path_factory.mktemp("re"),
+                              flags=["-ffp-contract=off"], args=["quick"])
+    return rc, out
 
 
 def test_lean_epilogue_matches_plain(report):

@@ -2,42 +2,28 @@
 both bounds (and the timestamps the probe hands back) with a brute-force
 linear scan over every input class, and counts the bounds that needed the
 binary-search residue path. No GPU, nothing loaded into Python."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from verifier_run import run_verifier
+
 CLASSES = ["bench", "drop2", "drop10", "drop30", "geometric", "clusters",
            "allequal", "dupruns"]
+FIELDS = ("bounds", "residue", "mismatches")
 
 
 @pytest.fixture(scope="module")
 def report(tmp_path_factory):
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    exe = str(tmp_path_factory.mktemp("wb") / "verify_window_bounds")
-    subprocess.run([cxx, "-O2", "-std=c++17", "-o", exe,
-                    os.path.join(REPO, "tools", "verify_window_bounds.cpp")],
-                   check=True)
-    p = subprocess.run([exe], capture_output=True, text=True)
-    print(p.stdout)
-    print(p.stderr)
-    rows = {}
-    for m in re.finditer(r"class=(\w+) bounds=(\d+) residue=(\d+) mismatches=(\d+)",
-                         p.stdout):
-        rows[m.group(1)] = tuple(int(m.group(i)) for i in (2, 3, 4))
-    return p.returncode, rows
+    rc, _, rows = run_verifier("verify_window_bounds", tmp_path_factory.mktemp("wb"))
+    return rc, rows
 
 
 def test_bounds_match_linear_scan(report):
     rc, rows = report
     assert sorted(rows) == sorted(CLASSES)
-    for cls, (bounds, _, bad) in rows.items():
-        assert bounds > 10000, cls       # a few thousand offsets x 8 sizes
-        assert bad == 0, cls
+    for cls, row in rows.items():
+        assert tuple(row) == FIELDS, cls
+        assert row["bounds"] > 10000, cls    # a few thousand offsets x 8 sizes
+        assert row["mismatches"] == 0, cls
     assert rc == 0
 
 
@@ -46,4 +32,4 @@ def test_bench_law_needs_no_residue(report):
     plus the four-row probe brackets every bound: the binary-search fallback
     never runs. The other classes' counts are printed, not asserted."""
     _, rows = report
-    assert rows["bench"][1] == 0
+    assert rows["bench"]["residue"] == 0

@@ -8,14 +8,10 @@ that start before, inside and after the chunk. Window edges are placed
 exactly on rows and on runs of equal timestamps, the case the oracle cannot
 judge (tests/test_gpu_window_bounds.py's docstring), so it is checked only
 here. No GPU, nothing loaded into Python."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from verifier_run import run_verifier
+
 CLASSES = ["bench", "drop2", "drop10", "drop30", "grid", "geometric",
            "clusters", "allequal", "dupruns", "dupgrid"]
 FIELDS = ("offsets", "ties", "dupties", "windows", "wties", "wdupties",
@@ -24,26 +20,15 @@ FIELDS = ("offsets", "ties", "dupties", "windows", "wties", "wdupties",
 
 @pytest.fixture(scope="module")
 def report(tmp_path_factory):
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    exe = str(tmp_path_factory.mktemp("ws") / "verify_window_share")
-    subprocess.run([cxx, "-O2", "-std=c++17", "-o", exe,
-                    os.path.join(REPO, "tools", "verify_window_share.cpp")],
-                   check=True)
-    p = subprocess.run([exe], capture_output=True, text=True)
-    print(p.stdout)
-    print(p.stderr)
-    rows = {}
-    pat = r"class=(\w+) " + " ".join(f + r"=(\d+)" for f in FIELDS)
-    for m in re.finditer(pat, p.stdout):
-        rows[m.group(1)] = dict(zip(FIELDS, map(int, m.groups()[1:])))
-    return p.returncode, rows
+    rc, _, rows = run_verifier("verify_window_share", tmp_path_factory.mktemp("ws"))
+    return rc, rows
 
 
 def test_share_matches_linear_scan(report):
     rc, rows = report
     assert sorted(rows) == sorted(CLASSES)
     for cls, row in rows.items():
+        assert tuple(row) == FIELDS, cls
         assert row["offsets"] > 20000, cls
         # 11 sizes x 2 steps x 6 ratios x 6 window counts x >= 4 query starts
         assert row["windows"] > 500000, cls

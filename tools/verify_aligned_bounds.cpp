@@ -30,28 +30,14 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
-#include <string>
 #include <vector>
 
-#include "../filodb_amd/csrc/fast_desc.h"
 #include "../filodb_amd/csrc/window_bounds.h"
-#include "../include/filodb_amd.h"
+#include "verify_kit_store.h"
 
 namespace {
 
-struct Rng {                       // splitmix64: deterministic everywhere
-  uint64_t s;
-  uint64_t next() {
-    uint64_t z = (s += 0x9e3779b97f4a7c15ULL);
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
-    return z ^ (z >> 31);
-  }
-  int64_t range(int64_t lo, int64_t hi) {      // inclusive
-    return lo + (int64_t)(next() % (uint64_t)(hi - lo + 1));
-  }
-  double unit() { return (double)(next() >> 11) / 9007199254740992.0; }
-};
+using kit::Rng;
 
 const int kSizes[] = {1, 2, 3, 4, 5, 6, 7, 8, 63, 64, 65, 240, 400};
 const int kM[] = {1, 20, 40, 64};
@@ -59,80 +45,9 @@ const int64_t kQ = 15000;
 const int64_t kT0 = 10000000;      // a multiple of kQ: the scrape grid's origin
 const int64_t kPhases[] = {0, 1, kQ / 2, kQ - 1, -1};
 
-std::vector<int64_t> grid(Rng& r, int n, int64_t interval, int64_t jitter) {
-  std::vector<int64_t> t((size_t)n);
-  for (int i = 0; i < n; i++)
-    t[(size_t)i] = kT0 + interval * i + (jitter ? r.range(-jitter, jitter) : 0);
-  return t;
-}
-
-std::vector<int64_t> make(const std::string& cls, Rng& r, int n) {
-  std::vector<int64_t> t;
-  if (cls == "bench") t = grid(r, n, kQ, 300);
-  else if (cls == "zerojitter") t = grid(r, n, kQ, 0);       // every row a tie
-  else if (cls == "driftm1") t = grid(r, n, kQ - 1, 100);
-  else if (cls == "driftp1") t = grid(r, n, kQ + 1, 100);
-  else if (cls == "driftm5") t = grid(r, n, kQ - 5, 0);
-  else if (cls == "driftp5") t = grid(r, n, kQ + 5, 0);
-  else if (cls == "dups") {
-    // a late row and the next, early one share a timestamp: 0.55 q after one
-    // grid point is 0.45 q before the next, and both stay inside C
-    t = grid(r, n, kQ, 50);
-    for (int i = 0; i + 1 < n; i += (int)r.range(2, 5)) {
-      t[(size_t)i] = kT0 + kQ * i + (kQ * 11) / 20;
-      t[(size_t)i + 1] = t[(size_t)i];
-    }
-  } else if (cls == "drop") {                  // a scrape grid with rows missing
-    for (int64_t j = 0; (int)t.size() < n; j++) {
-      if (j > 0 && r.unit() < 0.05) continue;
-      t.push_back(kT0 + j * kQ + r.range(-300, 300));
-    }
-  } else if (cls == "irregular") {
-    int64_t x = kT0;
-    for (int i = 0; i < n; i++) { t.push_back(x); x += r.range(1, 40000); }
-  } else if (cls == "interval10s") {
-    t = grid(r, n, 10000, 300);
-  } else if (cls == "widejitter") {            // residuals around +-0.6 q
-    t = grid(r, n, kQ, 9000);
-  }
-  for (size_t i = 1; i < t.size(); i++)        // nondecreasing, like the store
-    if (t[i] < t[i - 1]) t[i] = t[i - 1];
-  return t;
-}
-
 struct Totals {
   long cases = 0, eligible = 0, c_holds = 0, rejected_c = 0, windows = 0, mism = 0;
 };
-
-// one series' timestamps as the kernel holds them, from the descriptor alone
-bool decode_tso(const uint8_t* blob, const fdb_dir_entry_t& e, const FdbFastDesc& d,
-                std::vector<int32_t>& buf) {
-  const int n = d.n;
-  buf.assign((size_t)n + 2, 0x5a5a5a5a);
-  buf[0] = INT32_MIN + 7;                                  // tso[-1]: garbage
-  buf[(size_t)n + 1] = 12345;                              // tso[n]: garbage
-  const FdbFdVec tv = fdb_fd_open(blob + e.ts_off);
-  const uint8_t* idata = blob + e.ts_off + tv.payload;
-  for (int i = 0; i < n; i++) {
-    int64_t t;
-    if (tv.cls == FDB_FD_RAW64) { memcpy(&t, idata + 8 * (size_t)i, 8); t -= d.ts0; }
-    else t = (int64_t)d.ts_base + (int64_t)d.ts_slope * i +
-             (tv.cls == FDB_FD_PACKED
-                  ? fdb_fd_inner(idata, tv.nbits, (tv.flags & FDB_FD_SIGN) != 0, i) : 0);
-    if (t < 0 || t > INT32_MAX) return false;
-    buf[(size_t)i + 1] = (int32_t)t;
-  }
-  return true;
-}
-
-int brute_e(const int32_t* tso, int n, int64_t x) {
-  for (int i = n - 1; i >= 0; i--) if (tso[i] <= x) return i;
-  return -1;
-}
-int brute_s(const int32_t* tso, int n, int64_t y) {
-  for (int i = 0; i < n; i++) if (tso[i] >= y) return i;
-  return n;
-}
 
 // the kernel's sequence for one (series, query); returns eligibility
 bool check_query(const char* cls, const FdbFastDesc& d, const int32_t* tso,
@@ -154,8 +69,7 @@ bool check_query(const char* cls, const FdbFastDesc& d, const int32_t* tso,
   if (al.ok) t.eligible++;
   if (c && !al.ok) t.rejected_c++;
   if (al.ok && !c) {
-    if (t.mism < 10) fprintf(stderr, "UNSOUND class=%s n=%d k0=%d\n", cls, n, k0);
-    t.mism++;
+    kit::mismatch(t.mism, "UNSOUND class=%s n=%d k0=%d\n", cls, n, k0);
     return true;
   }
   if (!al.ok || !compare) return al.ok;
@@ -166,18 +80,22 @@ bool check_query(const char* cls, const FdbFastDesc& d, const int32_t* tso,
     int e, s;
     fdb_aligned_bounds(tso, n, al.k0, w, m, x, y, &e, &s, &t1, &t2);
     const int64_t xw = (int64_t)w * q - A, yw = xw - (int64_t)m * q;
-    const int we = brute_e(tso, n, xw), wsr = brute_s(tso, n, yw);
+    const int we = kit::brute_e(tso, n, xw), wsr = kit::brute_s(tso, n, yw);
     t.windows++;
     const bool ok = e == we && s == wsr && (e < 0 || t2 == tso[e]) &&
                     (s >= n || t1 == tso[s]);
-    if (!ok) {
-      if (t.mism < 10)
-        fprintf(stderr, "MISMATCH class=%s n=%d m=%d w=%d: e=%d want %d, s=%d want %d "
-                "(t2=%d t1=%d)\n", cls, n, m, w, e, we, s, wsr, t2, t1);
-      t.mism++;
-    }
+    if (!ok)
+      kit::mismatch(t.mism, "MISMATCH class=%s n=%d m=%d w=%d: e=%d want %d, s=%d want %d "
+                    "(t2=%d t1=%d)\n", cls, n, m, w, e, we, s, wsr, t2, t1);
   }
   return true;
+}
+
+void report(const char* cls, const Totals& t) {
+  kit::report_line("class", cls,
+                   {{"cases", t.cases}, {"eligible", t.eligible}, {"c_holds", t.c_holds},
+                    {"rejected_c", t.rejected_c}, {"windows", t.windows},
+                    {"mismatches", t.mism}});
 }
 
 }  // namespace
@@ -187,29 +105,27 @@ int main() {
                            "driftp5", "dups", "widejitter", "drop", "irregular",
                            "interval10s"};
   long total_bad = 0;
+  std::vector<int32_t> buf;
   for (const char* cls : classes) {
     Rng r{0xa11ULL * 1000003ULL + strlen(cls) * 7919ULL + (uint64_t)cls[0]};
+    // this tool's "drop" keeps row 0; the scrape family's drop laws do not
+    const char* law = strcmp(cls, "drop") ? cls : "drop5keep0";
     fdb_store_t* st = fdb_store_create(0);
-    std::vector<std::vector<int64_t>> tss;
+    std::vector<int> sizes;
     for (int n : kSizes)
       for (int rep = 0; rep < 3; rep++) {
-        tss.push_back(make(cls, r, n));
-        const std::vector<double> v((size_t)n, 1.0);
-        const int32_t sid = fdb_store_add_series(st, 0, FDB_COL_GAUGE);
-        fdb_series_append(st, sid, tss.back().data(), v.data(), n);
+        kit::add_series(st, FDB_COL_GAUGE, kit::make_ts(law, r, n, kT0, kQ, false),
+                        std::vector<double>((size_t)n, 1.0));
+        sizes.push_back(n);
       }
-    fdb_store_seal(st);
     fdb_view_t view;
-    if (fdb_store_view(st, &view) != FDB_OK) { fprintf(stderr, "%s: no view\n", cls); return 1; }
-    const fdb_dir_entry_t* dir = (const fdb_dir_entry_t*)view.dir;
+    if (!kit::sealed_view(cls, st, &view)) return 1;
     Totals t;
-    std::vector<int32_t> buf;
     for (int32_t sid = 0; sid < view.num_series; sid++) {
-      if (view.series_nchunks[sid] != 1) { t.mism++; continue; }
-      const fdb_dir_entry_t& e = dir[view.series_first[sid]];
       FdbFastDesc d;
-      fdb_build_fast_desc(view.blob, e.ts_off, e.val_off, e.num_rows, &d);
-      if (d.n != (int)tss[(size_t)sid].size() || !decode_tso(view.blob, e, d, buf)) {
+      const fdb_dir_entry_t* e = kit::series_desc(view, sid, &d);
+      if (view.series_nchunks[sid] != 1 || d.n != sizes[(size_t)sid] ||
+          !kit::decode_tso(view.blob, *e, d, buf)) {
         t.mism++;
         continue;
       }
@@ -219,9 +135,7 @@ int main() {
           check_query(cls, d, buf.data() + 1, kT0 - 10 * kQ + ph,
                       kQ, m, nw, true, t);
     }
-    printf("class=%s cases=%ld eligible=%ld c_holds=%ld rejected_c=%ld windows=%ld "
-           "mismatches=%ld\n", cls, t.cases, t.eligible, t.c_holds, t.rejected_c,
-           t.windows, t.mism);
+    report(cls, t);
     total_bad += t.mism;
     fdb_store_destroy(st);
   }
@@ -232,30 +146,23 @@ int main() {
     fdb_store_t* st = fdb_store_create(0);
     fdb_synth_generate(st, FDB_COL_COUNTER, 20000, 240, 100000, 15000, 300, 10.0, 0.001,
                        1000, 42);
-    fdb_store_seal(st);
     fdb_view_t view;
-    if (fdb_store_view(st, &view) != FDB_OK) { fprintf(stderr, "bench: no view\n"); return 1; }
-    const fdb_dir_entry_t* dir = (const fdb_dir_entry_t*)view.dir;
+    if (!kit::sealed_view("bench", st, &view)) return 1;
     Totals t;
     long eligible = 0;
-    std::vector<int32_t> buf;
     for (int32_t sid = 0; sid < view.num_series; sid++) {
-      const fdb_dir_entry_t& e = dir[view.series_first[sid]];
       FdbFastDesc d;
-      fdb_build_fast_desc(view.blob, e.ts_off, e.val_off, e.num_rows, &d);
-      if (!decode_tso(view.blob, e, d, buf)) { t.mism++; continue; }
+      const fdb_dir_entry_t* e = kit::series_desc(view, sid, &d);
+      if (!e || !kit::decode_tso(view.blob, *e, d, buf)) { t.mism++; continue; }
       if (check_query("benchlaw", d, buf.data() + 1, 100000, 15000, 20, 241,
                       sid < 2000, t))
         eligible++;
     }
-    printf("class=benchlaw cases=%ld eligible=%ld c_holds=%ld rejected_c=%ld windows=%ld "
-           "mismatches=%ld\n", t.cases, t.eligible, t.c_holds, t.rejected_c, t.windows,
-           t.mism);
+    report("benchlaw", t);
     printf("bench-law series eligible: %ld of %d\n", eligible, view.num_series);
     total_bad += t.mism;
     if (eligible != view.num_series) total_bad++;
     fdb_store_destroy(st);
   }
-  printf(total_bad ? "FAILED\n" : "OK\n");
-  return total_bad == 0 ? 0 : 1;
+  return kit::exit_status(total_bad, true);
 }

@@ -31,27 +31,13 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
-#include <string>
 #include <vector>
 
-#include "../filodb_amd/csrc/fast_desc.h"
-#include "../include/filodb_amd.h"
+#include "verify_kit_store.h"
 
 namespace {
 
-struct Rng {                       // splitmix64: deterministic everywhere
-  uint64_t s;
-  uint64_t next() {
-    uint64_t z = (s += 0x9e3779b97f4a7c15ULL);
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
-    return z ^ (z >> 31);
-  }
-  int64_t range(int64_t lo, int64_t hi) {      // inclusive
-    return lo + (int64_t)(next() % (uint64_t)(hi - lo + 1));
-  }
-  double unit() { return (double)(next() >> 11) / 9007199254740992.0; }
-};
+using kit::Rng;
 
 const int kSizes[] = {1, 2, 3, 4, 5, 63, 64, 65, 240, 255, 256, 257, 399, 400};
 const int64_t kT0 = 10000000;
@@ -212,19 +198,14 @@ const int32_t kSentT = 0x5a5a5a5a;
 const double kSentV = -7.25e300;
 
 void check_series(const fdb_view_t& view, int32_t sid, Totals& t) {
-  const fdb_dir_entry_t* dir = (const fdb_dir_entry_t*)view.dir;
   const uint8_t* blob = view.blob;
-  const bool has = view.series_nchunks[sid] >= 1;
-  const fdb_dir_entry_t* e = has ? &dir[view.series_first[sid]] : nullptr;
   FdbFastDesc d;
-  fdb_build_fast_desc(blob, has ? e->ts_off : 0, has ? e->val_off : 0,
-                      has ? e->num_rows : 0, &d);
+  const fdb_dir_entry_t* e = kit::series_desc(view, sid, &d);
   t.series++;
   auto bad = [&](const char* what) {
-    if (t.mism < 10) fprintf(stderr, "series %d: %s\n", sid, what);
-    t.mism++;
+    kit::mismatch(t.mism, "series %d: %s\n", sid, what);
   };
-  if (!has) {
+  if (!e) {
     if (d.n != 0) bad("n of an empty series");
     if (d.ts_rmin <= d.ts_rmax) bad("ts_rmin/ts_rmax of an empty series");
     return;
@@ -369,23 +350,20 @@ std::vector<uint8_t> enc_ddv_s8(const std::vector<int64_t>& ts) {   // signed 8-
 }
 
 int report(const char* name, fdb_store_t* st, long* exact_out = nullptr) {
-  fdb_store_seal(st);
   fdb_view_t view;
-  if (fdb_store_view(st, &view) != FDB_OK) { fprintf(stderr, "%s: no view\n", name); return 1; }
+  if (!kit::sealed_view(name, st, &view)) return 1;
   Totals t;
   for (int32_t sid = 0; sid < view.num_series; sid++) check_series(view, sid, t);
-  printf("store=%s series=%ld fields=%ld rows=%ld exact32=%ld resid=%ld overread=%d "
-         "mismatches=%ld\n", name, t.series, t.fields, t.rows, t.exact32, t.resid, t.over,
-         t.mism);
+  kit::report_line("store", name,
+                   {{"series", t.series}, {"fields", t.fields}, {"rows", t.rows},
+                    {"exact32", t.exact32}, {"resid", t.resid}, {"overread", t.over},
+                    {"mismatches", t.mism}});
   if (exact_out) *exact_out = t.exact32;
   fdb_store_destroy(st);
   return (t.mism != 0 || t.over > 6) ? 1 : 0;
 }
 
-void add(fdb_store_t* st, int kind, const std::vector<int64_t>& ts, const std::vector<double>& v) {
-  const int32_t sid = fdb_store_add_series(st, 0, kind);
-  fdb_series_append(st, sid, ts.data(), v.data(), (int32_t)ts.size());
-}
+using kit::add_series;
 
 std::vector<double> counter(Rng& r, int n) {
   std::vector<double> v((size_t)n);
@@ -405,7 +383,7 @@ int main() {
                        {"t32", 3000000, -(1 << 30) / 1024, (int64_t)1 << 20}};
   for (const Law& l : tlaws) {
     fdb_store_t* st = fdb_store_create(0);
-    for (int n : kSizes) add(st, FDB_COL_COUNTER, line(r, n, kT0, l.step, l.lo, l.hi), counter(r, n));
+    for (int n : kSizes) add_series(st, FDB_COL_COUNTER, line(r, n, kT0, l.step, l.lo, l.hi), counter(r, n));
     rc |= report(l.name, st);
   }
   for (int enc = 0; enc < 2; enc++) {            // hand-encoded: signed 8-bit, raw i64
@@ -413,11 +391,10 @@ int main() {
     std::vector<std::vector<int64_t>> tss;
     for (int n : kSizes) {
       tss.push_back(enc ? line(r, n, kT0, 15000, -300, 300) : line(r, n, kT0, 1000, -120, 100));
-      add(tmp, FDB_COL_COUNTER, tss.back(), counter(r, n));
+      add_series(tmp, FDB_COL_COUNTER, tss.back(), counter(r, n));
     }
-    fdb_store_seal(tmp);
     fdb_view_t tv;
-    fdb_store_view(tmp, &tv);
+    if (!kit::sealed_view("tmp", tmp, &tv)) return 1;
     const fdb_dir_entry_t* dir = (const fdb_dir_entry_t*)tv.dir;
     fdb_store_t* st = fdb_store_create(0);
     for (size_t i = 0; i < tss.size(); i++) {
@@ -448,7 +425,7 @@ int main() {
     fdb_store_t* st = fdb_store_create(0);
     for (int n : kSizes) {
       const std::vector<int64_t> lv = line(r, n, l.init, l.slope, l.lo, l.hi);
-      add(st, FDB_COL_GAUGE, line(r, n, kT0, 15000, -300, 300), std::vector<double>(lv.begin(), lv.end()));
+      add_series(st, FDB_COL_GAUGE, line(r, n, kT0, 15000, -300, 300), std::vector<double>(lv.begin(), lv.end()));
     }
     long ex = 0;
     rc |= report(l.name, st, &ex);
@@ -465,14 +442,14 @@ int main() {
     for (int n : kSizes) {
       std::vector<double> v((size_t)n);
       for (double& x : v) x = r.unit() * 100 + 0.25;
-      add(st, FDB_COL_GAUGE, line(r, n, kT0, 15000, -300, 300), v);
+      add_series(st, FDB_COL_GAUGE, line(r, n, kT0, 15000, -300, 300), v);
     }
     rc |= report("vraw", st);
     st = fdb_store_create(0);
     for (int n : kSizes) {
       std::vector<double> v = counter(r, n);
       if (n >= 3) for (int i = n / 2; i < n; i++) v[(size_t)i] -= v[(size_t)n / 2];
-      add(st, FDB_COL_COUNTER, line(r, n, kT0, 15000, -300, 300), v);
+      add_series(st, FDB_COL_COUNTER, line(r, n, kT0, 15000, -300, 300), v);
     }
     rc |= report("vresets", st);
   }
@@ -490,7 +467,7 @@ int main() {
       bool fits = true;                                  // stay exactly representable
       for (int64_t x : lv) fits = fits && std::llabs(x) < ((int64_t)1 << 53);
       if (!fits) continue;
-      add(st, r.range(0, 1) ? FDB_COL_COUNTER : FDB_COL_GAUGE,
+      add_series(st, r.range(0, 1) ? FDB_COL_COUNTER : FDB_COL_GAUGE,
           line(r, n, kT0, tstep, (tb == 2) ? -trange[tb] : 0, trange[tb]),
           std::vector<double>(lv.begin(), lv.end()));
     }
@@ -503,6 +480,5 @@ int main() {
     rc |= report("bench", st, &ex);
     printf("bench-law series with val_exact32: %ld of 20000\n", ex);
   }
-  printf(rc ? "FAILED\n" : "OK\n");
-  return rc;
+  return kit::exit_status(rc, true);
 }

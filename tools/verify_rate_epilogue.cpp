@@ -38,22 +38,11 @@
 
 #include "../filodb_amd/csrc/rate_core.h"
 #include "../filodb_amd/csrc/window_bounds.h"
+#include "verify_kit.h"
 
 namespace {
 
-struct Rng {                       // splitmix64: deterministic everywhere
-  uint64_t s;
-  uint64_t next() {
-    uint64_t z = (s += 0x9e3779b97f4a7c15ULL);
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
-    return z ^ (z >> 31);
-  }
-  int64_t range(int64_t lo, int64_t hi) {      // inclusive
-    return lo + (int64_t)(next() % (uint64_t)(hi - lo + 1));
-  }
-  double unit() { return (double)(next() >> 11) / 9007199254740992.0; }
-};
+using kit::Rng;
 
 uint64_t bits(double x) { uint64_t u; memcpy(&u, &x, 8); return u; }
 
@@ -97,11 +86,9 @@ void check_core(const CoreIn& c, const double* rk, CoreTally& ty) {
   if (c.ns - 1 < c.lim) ty.table++;
   if (bits(a) != bits(b)) {
 #pragma omp critical
-    if (ty.bad < 10)
-      fprintf(stderr, "CORE MISMATCH dts=%a dte=%a si=%a ns=%d v1=%a v2=%a "
-              "counter=%d lim=%d: plain %a lean %a\n", c.dts, c.dte, c.si, c.ns,
-              c.v1, c.v2, (int)c.counter, c.lim, a, b);
-    ty.bad++;
+    kit::mismatch(ty.bad, "CORE MISMATCH dts=%a dte=%a si=%a ns=%d v1=%a v2=%a "
+                  "counter=%d lim=%d: plain %a lean %a\n", c.dts, c.dte, c.si, c.ns,
+                  c.v1, c.v2, (int)c.counter, c.lim, a, b);
   }
 }
 
@@ -190,33 +177,9 @@ CoreTally check_cores(long long rounds, int64_t max_ms) {
 }
 
 // ---- 3. the seed early-out -----------------------------------------------------
-// timestamp laws of verify_window_share.cpp, offsets from row 0
-std::vector<int32_t> make_tso(int law, Rng& r, int n) {
-  std::vector<int64_t> t;
-  int64_t x = 0;
-  for (int i = 0; (int)t.size() < n; i++) {
-    switch (law) {
-      case 0: t.push_back((int64_t)i * 15000 + r.range(-300, 300)); break;   // bench
-      case 1: t.push_back((int64_t)i * 15000); break;                        // grid
-      case 2: if (r.unit() >= 0.30) t.push_back((int64_t)i * 15000 + r.range(-300, 300));
-              break;                                                         // drop30
-      case 3: t.push_back(x); x += (i == n / 2 - 1) ? ((int64_t)1 << 30)
-                                                    : r.range(900, 1100); break;
-      case 4: t.push_back(0); break;                                         // allequal
-      default: {                                                             // dupruns
-        const int run = (int)r.range(1, 5);
-        for (int k = 0; k < run && (int)t.size() < n; k++) t.push_back(x);
-        x += 15000 + r.range(-300, 300);
-      }
-    }
-  }
-  for (size_t i = 1; i < t.size(); i++) if (t[i] < t[i - 1]) t[i] = t[i - 1];
-  std::vector<int32_t> tso((size_t)(n > 4 ? n : 4));   // the header's contract
-  for (size_t i = 0; i < tso.size(); i++)
-    tso[i] = i < (size_t)n ? (int32_t)(t[i] - t[0])
-                           : (int32_t)(r.next() & 1 ? INT32_MIN : 12345);
-  return tso;
-}
+// six of verify_window_share.cpp's timestamp laws, offsets from row 0
+const char* const kSeedLaws[] = {"bench", "grid", "drop30", "clusters", "allequal",
+                                 "dupruns"};
 
 struct SeedTally { long long early = 0, searched = 0, nonzero = 0, bad = 0; };
 
@@ -227,7 +190,8 @@ SeedTally check_seed() {
   for (int law = 0; law < 6; law++)
     for (int n : sizes) {
       Rng r{0x5eedULL + (uint64_t)law * 7919ULL + (uint64_t)n};
-      const std::vector<int32_t> tso = make_tso(law, r, n);
+      const std::vector<int32_t> tso =      // max(n, 4) cells: the header's contract
+          kit::tso_exact(kit::make_ts(kSeedLaws[law], r, n, 0, 15000, true), r);
       const FdbLin lin = fdb_bounds_prepare(tso.data(), n);
       for (int64_t qstep : steps) {
         std::vector<int64_t> aes;
@@ -249,13 +213,10 @@ SeedTally check_seed() {
                                              &unused);
             if (early) {
               ty.early++;
-              if (e != -1 || s != 0) {
-                if (ty.bad < 10)
-                  fprintf(stderr, "SEED MISMATCH law=%d n=%d qstep=%lld Ae=%lld "
-                          "lane=%d: e=%d s=%d\n", law, n, (long long)qstep,
-                          (long long)Ae, lane, e, s);
-                ty.bad++;
-              }
+              if (e != -1 || s != 0)
+                kit::mismatch(ty.bad, "SEED MISMATCH law=%d n=%d qstep=%lld Ae=%lld "
+                              "lane=%d: e=%d s=%d\n", law, n, (long long)qstep,
+                              (long long)Ae, lane, e, s);
             } else {
               ty.searched++;
               if (s != 0) ty.nonzero++;
@@ -289,5 +250,5 @@ int main(int argc, char** argv) {
   const bool vacuous = ct.skip == 0 || ct.table == 0 || st.early == 0 ||
                        st.nonzero == 0;
   if (vacuous) fprintf(stderr, "a guarded path was never taken\n");
-  return (tbad || ct.bad || st.bad || vacuous) ? 1 : 0;
+  return kit::exit_status(tbad || ct.bad || st.bad || vacuous);
 }

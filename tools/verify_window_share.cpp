@@ -23,84 +23,20 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
-#include <string>
 #include <vector>
 
 #include "../filodb_amd/csrc/window_bounds.h"
+#include "verify_kit.h"
 
 namespace {
 
-struct Rng {                       // splitmix64: deterministic everywhere
-  uint64_t s;
-  uint64_t next() {
-    uint64_t z = (s += 0x9e3779b97f4a7c15ULL);
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
-    return z ^ (z >> 31);
-  }
-  int64_t range(int64_t lo, int64_t hi) {      // inclusive
-    return lo + (int64_t)(next() % (uint64_t)(hi - lo + 1));
-  }
-  double unit() { return (double)(next() >> 11) / 9007199254740992.0; }
-};
+using kit::Rng;
+using kit::brute_e;
+using kit::brute_s;
 
 const int kSizes[] = {0, 1, 2, 3, 4, 5, 63, 64, 65, 240, 400};
 const int kRatios[] = {1, 2, 20, 40, 63, 64};
 const int kWindows[] = {1, 64, 65, 256, 257, 600};
-
-// scrape grid 15 s +- 300 ms with a fraction `drop` of the rows deleted
-std::vector<int64_t> scrape(Rng& r, int n, double drop) {
-  std::vector<int64_t> t;
-  for (int64_t j = 0; (int)t.size() < n; j++) {
-    if (drop > 0 && r.unit() < drop) continue;
-    t.push_back(j * 15000 + r.range(-300, 300));
-  }
-  return t;
-}
-
-// the classes of verify_window_bounds.cpp, plus "grid" (every row exactly on
-// a 15 s edge) and "dupgrid" (runs of 1..5 equal rows exactly on 15 s edges)
-std::vector<int64_t> make(const std::string& cls, Rng& r, int n) {
-  std::vector<int64_t> t;
-  if (cls == "bench") t = scrape(r, n, 0.0);
-  else if (cls == "drop2") t = scrape(r, n, 0.02);
-  else if (cls == "drop10") t = scrape(r, n, 0.10);
-  else if (cls == "drop30") t = scrape(r, n, 0.30);
-  else if (cls == "grid") {
-    for (int i = 0; i < n; i++) t.push_back((int64_t)i * 15000);
-  } else if (cls == "geometric") {       // gaps double, restarting every 21 rows
-    int64_t x = 0;
-    for (int i = 0; i < n; i++) { t.push_back(x); x += (int64_t)1 << (i % 21); }
-  } else if (cls == "clusters") {        // two dense clusters, one 2^30 ms gap
-    int64_t x = 0;
-    for (int i = 0; i < n; i++) {
-      t.push_back(x);
-      x += (i == n / 2 - 1) ? ((int64_t)1 << 30) : r.range(900, 1100);
-    }
-  } else if (cls == "allequal") {
-    t.assign(n, 0);
-  } else if (cls == "dupruns" || cls == "dupgrid") {   // runs of 1..5 equal rows
-    int64_t x = 0;
-    while ((int)t.size() < n) {
-      int run = (int)r.range(1, 5);
-      for (int k = 0; k < run && (int)t.size() < n; k++) t.push_back(x);
-      x += 15000 + (cls == "dupgrid" ? 0 : r.range(-300, 300));
-    }
-  }
-  for (size_t i = 1; i < t.size(); i++)      // nondecreasing, like the store
-    if (t[i] < t[i - 1]) t[i] = t[i - 1];
-  for (size_t i = t.size(); i-- > 0;) t[i] -= t[0];   // offsets from row 0
-  return t;
-}
-
-int brute_e(const std::vector<int32_t>& tso, int n, int64_t x) {
-  for (int i = n - 1; i >= 0; i--) if (tso[i] <= x) return i;
-  return -1;
-}
-int brute_s(const std::vector<int32_t>& tso, int n, int64_t y) {
-  for (int i = 0; i < n; i++) if (tso[i] >= y) return i;
-  return n;
-}
 
 struct Tally {
   long offsets = 0, ties = 0, dupties = 0;        // derivation check
@@ -110,10 +46,8 @@ struct Tally {
 
 void report(const char* cls, int n, const char* what, long long a, long long b,
             int got, int want, Tally& ty) {
-  if (ty.bad < 10)
-    fprintf(stderr, "MISMATCH class=%s n=%d %s (%lld, %lld): got %d want %d\n",
-            cls, n, what, a, b, got, want);
-  ty.bad++;
+  kit::mismatch(ty.bad, "MISMATCH class=%s n=%d %s (%lld, %lld): got %d want %d\n",
+                cls, n, what, a, b, got, want);
 }
 
 // what a lane keeps from the end search at offset x: e(x), tso[e], and the
@@ -137,13 +71,13 @@ void check_offsets(const char* cls, const std::vector<int32_t>& tso, int n,
                    FdbLin lin, const std::vector<int64_t>& ys, Tally& ty) {
   for (int64_t y : ys) {
     const EndSearch r = end_search(tso, n, lin, y);
-    const int want = brute_s(tso, n, y);
+    const int want = brute_s(tso.data(), n, y);
     ty.offsets++;
     if (r.e >= 0 && tso[r.e] == y) {
       ty.ties++;
       if (r.e > 0 && tso[r.e - 1] == tso[r.e]) ty.dupties++;
     }
-    if (r.e != brute_e(tso, n, y)) report(cls, n, "e(y)", y, 0, r.e, brute_e(tso, n, y), ty);
+    if (r.e != brute_e(tso.data(), n, y)) report(cls, n, "e(y)", y, 0, r.e, brute_e(tso.data(), n, y), ty);
     else if (r.s_at_end != want) report(cls, n, "s(y)", y, 0, r.s_at_end, want, ty);
     else if (want < n && r.t_at_end != tso[want])
       report(cls, n, "tso[s(y)]", y, 0, r.t_at_end, tso[want], ty);
@@ -180,7 +114,7 @@ void check_exchange(const char* cls, const std::vector<int32_t>& tso, int n,
         const int64_t x = (int64_t)w * qstep - Ae;
         const int s = send[(lane - m) & 63];
         const int e = e_cur[lane];
-        const int we = brute_e(tso, n, x), wsr = brute_s(tso, n, x - qwindow);
+        const int we = brute_e(tso.data(), n, x), wsr = brute_s(tso.data(), n, x - qwindow);
         ty.windows++;
         if (wsr < n && tso[wsr] == x - qwindow) {      // start edge on a row
           ty.wties++;
@@ -209,13 +143,10 @@ int main() {
     Tally ty;
     for (int n : kSizes) {
       Rng r{0x5eedULL * 1000003ULL + (uint64_t)n * 7919ULL + strlen(cls)};
-      const std::vector<int64_t> t = make(cls, r, n);
-      // exactly max(n, 4) elements (the header's contract): an over-read is
-      // an address-sanitizer error; cells past n hold garbage on purpose
-      std::vector<int32_t> tso((size_t)(n > 4 ? n : 4));
-      for (size_t i = 0; i < tso.size(); i++)
-        tso[i] = i < (size_t)n ? (int32_t)t[i]
-                               : (int32_t)(r.next() & 1 ? INT32_MIN : 12345);
+      // scrape grid 15 s from 0, as offsets from row 0; exactly max(n, 4)
+      // elements, so an over-read is an address-sanitizer error
+      const std::vector<int32_t> tso =
+          kit::tso_exact(kit::make_ts(cls, r, n, 0, 15000, true), r);
       const int64_t span = n > 0 ? tso[n - 1] : 0;
       const FdbLin lin = fdb_bounds_prepare(tso.data(), n);
 
@@ -258,10 +189,11 @@ int main() {
               check_exchange(cls, tso, n, lin, Ae, qstep, m, nw, ty);
           }
     }
-    printf("class=%s offsets=%ld ties=%ld dupties=%ld windows=%ld wties=%ld "
-           "wdupties=%ld mismatches=%ld\n", cls, ty.offsets, ty.ties,
-           ty.dupties, ty.windows, ty.wties, ty.wdupties, ty.bad);
+    kit::report_line("class", cls,
+                     {{"offsets", ty.offsets}, {"ties", ty.ties}, {"dupties", ty.dupties},
+                      {"windows", ty.windows}, {"wties", ty.wties},
+                      {"wdupties", ty.wdupties}, {"mismatches", ty.bad}});
     total_bad += ty.bad;
   }
-  return total_bad == 0 ? 0 : 1;
+  return kit::exit_status(total_bad);
 }
