@@ -32,6 +32,9 @@ AGG_NONE, AGG_SUM, AGG_COUNT, AGG_MIN, AGG_MAX, AGG_AVG = 0, 1, 2, 3, 4, 5
 AGG_TOPK, AGG_BOTTOMK = 6, 7
 AGG_STDDEV, AGG_STDVAR, AGG_GROUP = 8, 9, 10
 AGG_QUANTILE, AGG_COUNT_VALUES = 11, 12
+# histogram present steps (FDB_HP_*; InstantFunction.scala:114-119)
+HP_QUANTILE, HP_QUANTILE_MINMAX, HP_MAX_QUANTILE = 0, 1, 2
+HP_BUCKET, HP_FRACTION, HP_FRACTION_MINMAX = 3, 4, 5
 # column kinds
 COL_GAUGE, COL_COUNTER, COL_HIST = 0, 1, 2
 
@@ -146,6 +149,15 @@ def lib():
             ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(Query),
             ctypes.c_int32, _c_double_p, _c_double_p, _c_double_p,
             _c_double_p, _c_double_p, ctypes.c_int32]
+        L.fdb_query_exec_hist_present.argtypes = [
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(Query),
+            ctypes.c_int32, ctypes.c_int32, _c_double_p, _c_double_p,
+            _c_double_p, _c_double_p, _c_double_p, ctypes.c_int32]
+        L.fdb_hist_present.argtypes = [
+            ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_double,
+            _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+            ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_double,
+            _c_double_p, ctypes.c_int32]
         L.fdb_brv2_builder_create.restype = ctypes.c_void_p
         L.fdb_brv2_builder_create.argtypes = [ctypes.c_int64]
         L.fdb_brv2_builder_destroy.argtypes = [ctypes.c_void_p]
@@ -405,6 +417,25 @@ class Engine:
             _as_f64_ptr(out_quantile), 1 if on_device else 0)
         _check(rc, "query_exec_hist_mm")
 
+    def query_hist_present(self, dataset, q: Query, num_buckets, present_id,
+                           out_present=None, out_bucket_sums=None,
+                           out_counts=None, out_max=None, out_min=None,
+                           on_device=False):
+        """Histogram scan plus one present step (HP_*) with p0 = q.param and
+        p1 = q.param2 over the dataset's bucket scheme. Returns out_present
+        ([num_groups * windows], allocated as numpy when None)."""
+        if out_present is None:
+            assert not on_device
+            out_present = np.empty(q.num_groups * q.num_windows,
+                                   dtype=np.float64)
+        rc = lib().fdb_query_exec_hist_present(
+            self._h, dataset._h, ctypes.byref(q), num_buckets, present_id,
+            _as_f64_ptr(out_bucket_sums), _as_f64_ptr(out_counts),
+            _as_f64_ptr(out_max), _as_f64_ptr(out_min),
+            _as_f64_ptr(out_present), 1 if on_device else 0)
+        _check(rc, "query_exec_hist_present")
+        return out_present
+
     def count_values(self, dataset, q: Query, k_cap=64):
         """CountValuesRowAggregator: per (group, window) distinct values with
         frequencies, sorted ascending. Returns (values, counts, n) with
@@ -469,6 +500,25 @@ def make_query(start, step, end, window, func_id, agg_id=AGG_NONE, num_groups=0,
     q.param = param
     q.param2 = param2
     return q
+
+
+def hist_present(engine, present_id, bucket_sums, counts, num_buckets,
+                 first, mult, p0=0.0, p1=0.0, maxs=None, mins=None, out=None,
+                 on_device=False):
+    """Standalone histogram present step (HP_*) over caller grids: bucket_sums
+    [cells * num_buckets] (numpy, or a device tensor with on_device), counts
+    [cells], maxs/mins [cells] for the min/max modes. Returns out [cells]."""
+    cells = int(counts.shape[0])
+    nb = num_buckets
+    if out is None:
+        assert not on_device
+        out = np.empty(cells, dtype=np.float64)
+    rc = lib().fdb_hist_present(
+        engine._h, present_id, p0, p1, _as_f64_ptr(bucket_sums),
+        _as_f64_ptr(counts), _as_f64_ptr(maxs), _as_f64_ptr(mins), cells, nb,
+        first, mult, _as_f64_ptr(out), 1 if on_device else 0)
+    _check(rc, "hist_present")
+    return out
 
 
 def nibblepack_unpack_doubles(data, n):

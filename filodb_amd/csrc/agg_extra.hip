@@ -217,6 +217,123 @@ __global__ void hist_quantile_kernel(const double* __restrict__ sums,
   out[i] = bucketStart + (bucketEnd - bucketStart) * (rank / count);
 }
 
+// --- histogram present step, every mode (FDB_HP_*) ---------------------------
+// One thread per cell over a geometric scheme: top(b) = first * pow(mult, b),
+// the expression hist_quantile_kernel uses, so FDB_HP_QUANTILE returns its
+// bits. A geometric scheme is never Base2ExpHistogramBuckets: interpolation is
+// linear and no top is +Inf.
+
+// Histogram.quantile(q, min, max) (Histogram.scala:65-108). clip = false is
+// hist_quantile_kernel's rule (no min/max step). The firstBucketGTE walk stops
+// at nb - 1, so a NaN sum cannot leave the cell; the reference's unbounded
+// walk ends there too for valid input (rank <= top).
+__device__ double hp_quantile(const double* __restrict__ v, int nb, double q,
+                              double first, double mult, bool clip,
+                              double mn, double mx) {
+  double top = v[nb - 1];
+  if (q < 0) return -INFINITY;
+  if (q > 1) return INFINITY;
+  if (nb < 2 || !(top > 0)) return NAN;
+  double rank = q * top;
+  int bucket = 0;
+  while (bucket < nb - 1 && v[bucket] < rank) bucket++;
+  double bucketStart = bucket == 0 ? 0 : first * pow(mult, bucket - 1);
+  double bucketEnd = first * pow(mult, bucket);
+  if (clip) {   // a NaN min/max compares false and clips nothing
+    if (mn > bucketStart && mn <= bucketEnd) bucketStart = mn;
+    if (mx > bucketStart && mx <= bucketEnd) bucketEnd = mx;
+  }
+  if (bucket == nb - 1 && isinf(bucketEnd)) return first * pow(mult, nb - 2);
+  if (bucket == 0 && first <= 0) return first;
+  double count = bucket == 0 ? v[0] : v[bucket] - v[bucket - 1];
+  rank -= bucket == 0 ? 0 : v[bucket - 1];
+  return bucketStart + (bucketEnd - bucketStart) * (rank / count);
+}
+
+// java.lang.Math.max/min: NaN if either argument is NaN
+__device__ __forceinline__ double hp_jmax(double a, double b) {
+  return (isnan(a) || isnan(b)) ? NAN : (a > b ? a : b);
+}
+__device__ __forceinline__ double hp_jmin(double a, double b) {
+  return (isnan(a) || isnan(b)) ? NAN : (a < b ? a : b);
+}
+
+// Histogram.histogramFraction(lower, upper, min, max) (Histogram.scala:119-197),
+// linear branch. The host has checked lower >= 0 && upper >= 0.
+__device__ double hp_fraction(const double* __restrict__ v, int nb,
+                              double lower, double upper,
+                              double first, double mult, double mn, double mx) {
+  const double count = v[nb - 1];
+  if (count == 0) return NAN;
+  if (lower == 0 && upper == 0) return v[0] / count;
+  if (lower >= upper) return 0.0;
+  double lowerRank = 0.0, upperRank = 0.0;
+  bool lowerSet = false, upperSet = false;
+  double bucketLower = 0.0, prevVal = 0.0;
+  for (int b = 0; b < nb && (!lowerSet || !upperSet); b++) {
+    const double bucketUpper = first * pow(mult, b);
+    const double val = v[b];
+    const double low = hp_jmax(bucketLower, mn);
+    const double high = hp_jmin(bucketUpper, mx);
+    if (!lowerSet && bucketLower == lower) { lowerRank = prevVal; lowerSet = true; }
+    if (!upperSet && bucketUpper == upper) { upperRank = val; upperSet = true; }
+    if (!lowerSet && bucketLower < lower && bucketUpper > lower) {
+      lowerRank = prevVal + (val - prevVal) * ((lower - low) / (high - low));
+      lowerSet = true;
+    }
+    if (!upperSet && bucketLower < upper && bucketUpper > upper) {
+      upperRank = prevVal + (val - prevVal) * ((upper - low) / (high - low));
+      upperSet = true;
+    }
+    bucketLower = bucketUpper;
+    prevVal = val;
+  }
+  if (!lowerSet || lowerRank > count) lowerRank = count;
+  if (!upperSet || upperRank > count) upperRank = count;
+  return (upperRank - lowerRank) / count;
+}
+
+// HistogramBucketImpl (InstantFunction.scala:433-453): the first bucket whose
+// top is within 1e-10 of le, else NaN
+__device__ double hp_bucket(const double* __restrict__ v, int nb, double le,
+                            double first, double mult) {
+  for (int b = 0; b < nb; b++)
+    if (fabs(first * pow(mult, b) - le) <= 1e-10) return v[b];
+  return NAN;
+}
+
+// maxs/mins are null unless the mode reads them (the host checks). cnt == 0 is
+// the reference's empty histogram: NaN in every mode.
+__global__ void hist_present_kernel(const double* __restrict__ sums,
+                                    const double* __restrict__ cnt,
+                                    const double* __restrict__ maxs,
+                                    const double* __restrict__ mins,
+                                    double* __restrict__ out,
+                                    size_t cells, int nb, int present_id,
+                                    double p0, double p1,
+                                    double first, double mult) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= cells) return;
+  if (!(cnt[i] > 0)) { out[i] = NAN; return; }
+  const double* v = sums + i * nb;
+  double r = NAN;
+  switch (present_id) {
+    case FDB_HP_QUANTILE:
+      r = hp_quantile(v, nb, p0, first, mult, false, 0, 0); break;
+    case FDB_HP_QUANTILE_MINMAX:
+      r = hp_quantile(v, nb, p0, first, mult, true, mins[i], maxs[i]); break;
+    case FDB_HP_MAX_QUANTILE:
+      r = hp_quantile(v, nb, p0, first, mult, true, 0, maxs[i]); break;
+    case FDB_HP_BUCKET:
+      r = hp_bucket(v, nb, p0, first, mult); break;
+    case FDB_HP_FRACTION:
+      r = hp_fraction(v, nb, p0, p1, first, mult, -INFINITY, INFINITY); break;
+    case FDB_HP_FRACTION_MINMAX:
+      r = hp_fraction(v, nb, p0, p1, first, mult, mins[i], maxs[i]); break;
+  }
+  out[i] = r;
+}
+
 __global__ void avg_div_kernel(double* __restrict__ out,
                                const double* __restrict__ a,
                                const double* __restrict__ b, size_t n) {
@@ -271,6 +388,51 @@ int32_t fdb_launch_hist_quantile(hipStream_t stream, const double* sums,
   hipLaunchKernelGGL(hist_quantile_kernel, blocks256(cells), dim3(256), 0,
                      stream, sums, cnt, out, cells, nb, q, first, mult);
   return launched("hist_quantile_kernel");
+}
+
+bool fdb_hist_present_needs_mm(int present_id) {
+  return present_id == FDB_HP_QUANTILE_MINMAX ||
+         present_id == FDB_HP_MAX_QUANTILE ||
+         present_id == FDB_HP_FRACTION_MINMAX;
+}
+
+// the argument rules of a present step, checked before anything is launched
+int32_t fdb_hist_present_check(int present_id, double p0, double p1,
+                               bool have_mm, int nb) {
+  if (present_id < FDB_HP_QUANTILE || present_id > FDB_HP_FRACTION_MINMAX) {
+    fdb_set_error("unknown histogram present id %d (FDB_HP_*)", present_id);
+    return FDB_ERR_BADARG;
+  }
+  if (nb < 1 || nb > 64) { fdb_set_error("num_buckets must be 1..64"); return FDB_ERR_BADARG; }
+  const bool fraction = present_id == FDB_HP_FRACTION ||
+                        present_id == FDB_HP_FRACTION_MINMAX;
+  if (fraction && !(p0 >= 0 && p1 >= 0)) {   // the reference's require; NaN fails it
+    fdb_set_error("lower & upper params should be >= 0: lower=%g, upper=%g", p0, p1);
+    return FDB_ERR_BADARG;
+  }
+  if (present_id == FDB_HP_BUCKET && std::isinf(p0) && p0 > 0) {
+    fdb_set_error("+Inf bucket not in the last position (a geometric scheme "
+                  "has no +Inf top)");
+    return FDB_ERR_BADARG;
+  }
+  if (fdb_hist_present_needs_mm(present_id) && !have_mm) {
+    fdb_set_error("histogram present id %d needs max and min inputs", present_id);
+    return FDB_ERR_BADARG;
+  }
+  return FDB_OK;
+}
+
+int32_t fdb_launch_hist_present(hipStream_t stream, const double* sums,
+                                const double* cnt, const double* maxs,
+                                const double* mins, double* out, size_t cells,
+                                int nb, int present_id, double p0, double p1,
+                                double first, double mult) {
+  if (int32_t rc = fdb_hist_present_check(present_id, p0, p1, maxs && mins, nb))
+    return rc;
+  hipLaunchKernelGGL(hist_present_kernel, blocks256(cells), dim3(256), 0,
+                     stream, sums, cnt, maxs, mins, out, cells, nb, present_id,
+                     p0, p1, first, mult);
+  return launched("hist_present_kernel");
 }
 
 int32_t fdb_launch_avg_div(hipStream_t stream, double* out, const double* a,

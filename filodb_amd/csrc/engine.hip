@@ -517,7 +517,8 @@ static int32_t run_hist(fdb_engine_t* e, const fdb_dataset_t* d,
                         const fdb_query_t* q, int32_t nb,
                         double* out_bucket_sums, double* out_counts,
                         double* out_max, double* out_min,
-                        double* out_quantile, int32_t out_on_device) {
+                        double* out_quantile, int32_t out_on_device,
+                        int32_t present_id = -1, double* out_present = nullptr) {
   HIP_CHECK(hipSetDevice(e->device));
   int nw;
   if (int32_t rc = check_windows(q, "bad hist query params", &nw)) return rc;
@@ -527,13 +528,38 @@ static int32_t run_hist(fdb_engine_t* e, const fdb_dataset_t* d,
     fdb_set_error("not a histogram dataset");
     return FDB_ERR_BADARG;
   }
-  const int hfunc = (q->func_id == FDB_FN_SUM_OVER_TIME) ? 1 : 0;
-  if (q->func_id != FDB_FN_HIST_RATE && q->func_id != FDB_FN_SUM_OVER_TIME) {
-    fdb_set_error("histogram queries support FDB_FN_HIST_RATE and "
-                  "FDB_FN_SUM_OVER_TIME (got %d)", q->func_id);
+  int hfunc;
+  switch (q->func_id) {
+    case FDB_FN_HIST_RATE:     hfunc = H2_RATE; break;
+    case FDB_FN_SUM_OVER_TIME: hfunc = H2_SUM; break;
+    case FDB_FN_INCREASE:      hfunc = H2_INCREASE; break;
+    case FDB_FN_LAST:          hfunc = H2_LAST; break;
+    default:
+      fdb_set_error("histogram queries support FDB_FN_HIST_RATE, "
+                    "FDB_FN_INCREASE, FDB_FN_SUM_OVER_TIME and FDB_FN_LAST "
+                    "(got %d)", q->func_id);
+      return FDB_ERR_BADARG;
+  }
+  if (hfunc == H2_INCREASE && (out_max || out_min)) {
+    // only Rate maps to RateAndMinMaxOverTime (RangeFunction.scala:383-385)
+    fdb_set_error("FDB_FN_INCREASE on a histogram has no max/min outputs");
     return FDB_ERR_BADARG;
   }
-  if ((out_max || out_min) && !d->has_mm) {
+  // a present step's arguments are checked before the scan runs; a mode that
+  // reads max/min scans the companion columns whether or not the caller asked
+  // for those grids
+  const bool present = out_present != nullptr;
+  const bool need_mm = present && fdb_hist_present_needs_mm(present_id);
+  if (present)
+    if (int32_t rc = fdb_hist_present_check(present_id, q->param, q->param2,
+                                            d->has_mm != 0, nb))
+      return rc;
+  if (need_mm && hfunc == H2_INCREASE) {
+    fdb_set_error("FDB_FN_INCREASE on a histogram has no max/min for present "
+                  "id %d", present_id);
+    return FDB_ERR_BADARG;
+  }
+  if ((out_max || out_min || need_mm) && !d->has_mm) {
     fdb_set_error("dataset has no max/min companion columns "
                   "(fdb_series_append_hist_mm)");
     return FDB_ERR_BADARG;
@@ -543,19 +569,25 @@ static int32_t run_hist(fdb_engine_t* e, const fdb_dataset_t* d,
 
   // caller-provided device outputs are wrapped, everything else is owned and
   // released on every exit
-  DevBuf dev_sums, dev_cnt, dev_quant, dev_max, dev_min;
+  DevBuf dev_sums, dev_cnt, dev_quant, dev_max, dev_min, dev_present;
   if (out_on_device) {
     dev_sums.wrap(out_bucket_sums);
     dev_cnt.wrap(out_counts);
     dev_quant.wrap(out_quantile);
     dev_max.wrap(out_max); dev_min.wrap(out_min);
+    dev_present.wrap(out_present);
   }
   if (!dev_sums && !dev_sums.alloc(cells * nb * 8)) return alloc_failed("hist query");
   if (!dev_cnt && !dev_cnt.alloc(cells * 8)) return alloc_failed("hist query");
   if (out_quantile && !dev_quant && !dev_quant.alloc(cells * 8))
     return alloc_failed("hist query");
+  if (present && !dev_present && !dev_present.alloc(cells * 8))
+    return alloc_failed("hist query");
   if (out_max && !dev_max &&
       (!dev_max.alloc(cells * 8) || !dev_min.alloc(cells * 8)))
+    return alloc_failed("hist query");
+  if (need_mm && ((!dev_max && !dev_max.alloc(cells * 8)) ||
+                  (!dev_min && !dev_min.alloc(cells * 8))))
     return alloc_failed("hist query");
   HIP_CHECK(hipMemsetAsync(dev_sums.get(), 0, cells * nb * 8, e->stream));
   HIP_CHECK(hipMemsetAsync(dev_cnt.get(), 0, cells * 8, e->stream));
@@ -572,17 +604,27 @@ static int32_t run_hist(fdb_engine_t* e, const fdb_dataset_t* d,
                                 dev_max.get(), dev_min.get());
   if (rc != FDB_OK) return rc;
 
-  if (out_quantile) {
+  if (out_quantile || present) {
     // bucket scheme (first, mult) from the first hist vector in the blob
     uint64_t voff0;
     HIP_CHECK(hipMemcpy(&voff0, d->val_off, 8, hipMemcpyDeviceToHost));
     double fm[2];
     HIP_CHECK(hipMemcpy(fm, d->blob + voff0 + FDB_HIST_OFF_DEF + 2, 16,
                         hipMemcpyDeviceToHost));
-    rc = fdb_launch_hist_quantile(e->stream, dev_sums.get(), dev_cnt.get(),
-                                  dev_quant.get(), cells, nb, q->param,
-                                  fm[0], fm[1]);
-    if (rc != FDB_OK) return rc;
+    if (out_quantile) {
+      rc = fdb_launch_hist_quantile(e->stream, dev_sums.get(), dev_cnt.get(),
+                                    dev_quant.get(), cells, nb, q->param,
+                                    fm[0], fm[1]);
+      if (rc != FDB_OK) return rc;
+    }
+    if (present) {
+      rc = fdb_launch_hist_present(e->stream, dev_sums.get(), dev_cnt.get(),
+                                   need_mm ? dev_max.get() : nullptr,
+                                   need_mm ? dev_min.get() : nullptr,
+                                   dev_present.get(), cells, nb, present_id,
+                                   q->param, q->param2, fm[0], fm[1]);
+      if (rc != FDB_OK) return rc;
+    }
   }
   HIP_CHECK(hipStreamSynchronize(e->stream));
   if (!out_on_device) {
@@ -592,6 +634,8 @@ static int32_t run_hist(fdb_engine_t* e, const fdb_dataset_t* d,
       HIP_CHECK(hipMemcpy(out_counts, dev_cnt.get(), cells * 8, hipMemcpyDeviceToHost));
     if (out_quantile)
       HIP_CHECK(hipMemcpy(out_quantile, dev_quant.get(), cells * 8, hipMemcpyDeviceToHost));
+    if (present)
+      HIP_CHECK(hipMemcpy(out_present, dev_present.get(), cells * 8, hipMemcpyDeviceToHost));
     if (out_max && dev_max)
       HIP_CHECK(hipMemcpy(out_max, dev_max.get(), cells * 8, hipMemcpyDeviceToHost));
     if (out_min && dev_min)
@@ -618,6 +662,66 @@ extern "C" int32_t fdb_query_exec_hist_mm(fdb_engine_t* e, const fdb_dataset_t* 
                                           double* out_quantile, int32_t out_on_device) {
   return run_hist(e, d, q, nb, out_bucket_sums, out_counts, out_max, out_min,
                   out_quantile, out_on_device);
+}
+
+// scan plus present step (FDB_HP_*) in one call: p0 = q->param, p1 = q->param2,
+// the scheme read from the dataset
+extern "C" int32_t fdb_query_exec_hist_present(
+    fdb_engine_t* e, const fdb_dataset_t* d, const fdb_query_t* q, int32_t nb,
+    int32_t present_id, double* out_bucket_sums, double* out_counts,
+    double* out_max, double* out_min, double* out_present,
+    int32_t out_on_device) {
+  if (!out_present) {
+    fdb_set_error("fdb_query_exec_hist_present: out_present is NULL");
+    return FDB_ERR_BADARG;
+  }
+  return run_hist(e, d, q, nb, out_bucket_sums, out_counts, out_max, out_min,
+                  nullptr, out_on_device, present_id, out_present);
+}
+
+// standalone presenter over caller grids (host or device pointers): what a
+// multi-GPU caller runs after all-reducing the bucket sums
+extern "C" int32_t fdb_hist_present(
+    fdb_engine_t* e, int32_t present_id, double p0, double p1,
+    const double* bucket_sums, const double* counts, const double* maxs,
+    const double* mins, int64_t cells, int32_t nb, double bucket_first,
+    double bucket_mult, double* out, int32_t on_device) {
+  HIP_CHECK(hipSetDevice(e->device));
+  if (!bucket_sums || !counts || !out || cells < 1) {
+    fdb_set_error("fdb_hist_present: bucket_sums, counts and out are "
+                  "required and cells must be >= 1");
+    return FDB_ERR_BADARG;
+  }
+  if (int32_t rc = fdb_hist_present_check(present_id, p0, p1, maxs && mins, nb))
+    return rc;
+  const bool need_mm = fdb_hist_present_needs_mm(present_id);
+  const size_t n = (size_t)cells;
+  DevBuf dsum, dcnt, dmax, dmin, dout;
+  if (on_device) {
+    dsum.wrap(const_cast<double*>(bucket_sums));
+    dcnt.wrap(const_cast<double*>(counts));
+    if (need_mm) { dmax.wrap(const_cast<double*>(maxs)); dmin.wrap(const_cast<double*>(mins)); }
+    dout.wrap(out);
+  } else {
+    if (!dsum.alloc(n * nb * 8) || !dcnt.alloc(n * 8) || !dout.alloc(n * 8) ||
+        (need_mm && (!dmax.alloc(n * 8) || !dmin.alloc(n * 8))))
+      return alloc_failed("hist present");
+    HIP_CHECK(hipMemcpyAsync(dsum.get(), bucket_sums, n * nb * 8, hipMemcpyHostToDevice, e->stream));
+    HIP_CHECK(hipMemcpyAsync(dcnt.get(), counts, n * 8, hipMemcpyHostToDevice, e->stream));
+    if (need_mm) {
+      HIP_CHECK(hipMemcpyAsync(dmax.get(), maxs, n * 8, hipMemcpyHostToDevice, e->stream));
+      HIP_CHECK(hipMemcpyAsync(dmin.get(), mins, n * 8, hipMemcpyHostToDevice, e->stream));
+    }
+  }
+  int32_t rc = fdb_launch_hist_present(e->stream, dsum.get(), dcnt.get(),
+                                       dmax.get(), dmin.get(), dout.get(), n,
+                                       nb, present_id, p0, p1, bucket_first,
+                                       bucket_mult);
+  if (rc != FDB_OK) return rc;
+  HIP_CHECK(hipStreamSynchronize(e->stream));
+  if (!on_device)
+    HIP_CHECK(hipMemcpy(out, dout.get(), n * 8, hipMemcpyDeviceToHost));
+  return FDB_OK;
 }
 
 extern "C" int32_t fdb_query_exec(fdb_engine_t* e, const fdb_dataset_t* d, const fdb_query_t* q,

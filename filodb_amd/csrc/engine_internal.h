@@ -126,7 +126,9 @@ int32_t fdb_launch_window_sample(hipStream_t stream, const uint8_t* blob,
                                  int num_windows, int func_id, double param,
                                  double param2, double* out, int32_t* overflow);
 
-// hist2.hip: two-cursor histogram walk (unbounded chunks / window ratio)
+// hist2.hip: two-cursor histogram walk (unbounded chunks / window ratio).
+// hfunc is the walk's window function.
+enum { H2_RATE = 0, H2_SUM = 1, H2_INCREASE = 2, H2_LAST = 3 };
 int32_t fdb_launch_hist2(hipStream_t stream, const uint8_t* blob, DirSoA dir,
                          const uint64_t* max_off, const uint64_t* min_off,
                          const int32_t* series_first,
@@ -153,6 +155,17 @@ int32_t fdb_launch_agg_present(hipStream_t stream, double* out,
 int32_t fdb_launch_hist_quantile(hipStream_t stream, const double* sums,
                                  const double* cnt, double* out, size_t cells,
                                  int nb, double q, double first, double mult);
+// histogram present step over [cells × nb] sums (FDB_HP_*; maxs/mins nullable).
+// The launcher runs fdb_hist_present_check itself; an entry point that scans
+// first calls it before the scan.
+bool fdb_hist_present_needs_mm(int present_id);
+int32_t fdb_hist_present_check(int present_id, double p0, double p1,
+                               bool have_mm, int nb);
+int32_t fdb_launch_hist_present(hipStream_t stream, const double* sums,
+                                const double* cnt, const double* maxs,
+                                const double* mins, double* out, size_t cells,
+                                int nb, int present_id, double p0, double p1,
+                                double first, double mult);
 int32_t fdb_launch_avg_div(hipStream_t stream, double* out, const double* a,
                            const double* b, size_t n);
 int32_t fdb_launch_quantile_cells(hipStream_t stream, const double* grid,

@@ -29,6 +29,19 @@
 // Histogram.compare's top-bucket-down order (Histogram.scala:204-214). A window
 // counts corrections from the entry of its start element's chunk: the
 // reference's per-window CorrectionMeta starts NoCorrection there.
+//
+// Increase (HistIncreaseFunction, RateFunctions.scala:415-418) is the rate walk
+// with the extrapolated delta left unscaled (isRate = false).
+//
+// Last sample (LastSampleChunkedFunctionH, RangeFunction.scala:630-641): the raw
+// buckets of the last element with ts in [wEnd - window, wEnd], no corrections.
+// Only the E cursor exists; it decodes section bases and the element a window
+// stops on, nothing else. With companion columns the cell's max/min are the
+// companion values at that row (LastSampleChunkedFunctionHMax, :643-682), not a
+// fold over the window. Divergence: where two chunks meet on an equal
+// timestamp the reference keeps the earlier chunk's row (ts > timestamp,
+// strictly) and this cursor lands on the later one — the documented
+// duplicate-timestamp boundary index choice (README).
 
 #include <cstring>
 #include <cmath>
@@ -120,12 +133,13 @@ __device__ __forceinline__ void h2_set_value(H2Cursor& cu, int64_t scan) {
   cu.decoded = true;
 }
 
-// HFUNC 0 = counter-corrected rate (HistRateFunction); 1 = SumOverTime of
-// the histograms (raw bucket sums — SumOverTimeChunkedFunctionH, no
-// corrections; both cursors then decode every element they pass and carry a
-// per-bucket running prefix). out_max/out_min (nullable) add the otel
-// companion-column max/min per window, merged across series with
-// maxIgnoreNaN/minIgnoreNaN (HistMaxMinSumAggregator).
+// HFUNC H2_RATE = counter-corrected rate (HistRateFunction); H2_SUM =
+// SumOverTime of the histograms (raw bucket sums — SumOverTimeChunkedFunctionH,
+// no corrections; both cursors then decode every element they pass and carry a
+// per-bucket running prefix); H2_INCREASE = the rate walk unscaled; H2_LAST =
+// the window's last raw sample, E cursor only. out_max/out_min (nullable) add
+// the otel companion-column max/min per window (H2_LAST: at the E row), merged
+// across series with maxIgnoreNaN/minIgnoreNaN (HistMaxMinSumAggregator).
 template <int MINW, int HFUNC>
 __global__ __launch_bounds__(H2_WAVES * 64, MINW)
 void hist2_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
@@ -148,6 +162,8 @@ void hist2_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
   const int lane = threadIdx.x & 63;
   const int b = lane;
   const bool live = b < nb;
+  constexpr bool IS_RATE = HFUNC == H2_RATE || HFUNC == H2_INCREASE;
+  constexpr bool IS_LAST = HFUNC == H2_LAST;
   const bool tmg = (abl & 8) != 0;   // s_memtime phase split into out_cnt[0..3]
   uint64_t tAdv = 0, tDec = 0, tEmit = 0, tc = 0;
 
@@ -226,7 +242,7 @@ void hist2_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
                                    cu.sbuf, off);
       int64_t scan = wave_incl_scan_i64(live ? delta : 0, lane);
       h2_set_value(cu, scan);
-      if (HFUNC == 1) cu.psum_b += cu.val_b;   // value prefix through current
+      if (HFUNC == H2_SUM) cu.psum_b += cu.val_b;   // value prefix through current
     };
 
     // step to the next element; returns false when the series is exhausted.
@@ -236,8 +252,10 @@ void hist2_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
         if (cu.c + 1 >= nchunks) return false;
         // leaving a chunk: its last element's raw value feeds the boundary
         // drop detection (and TypeDrop at the next chunk's head)
-        decode_cur(cu);
-        cu.prevlast_b = cu.val_b;
+        if (!IS_LAST) {
+          decode_cur(cu);
+          cu.prevlast_b = cu.val_b;
+        }
         open_chunk(cu, cu.c + 1, tsbuf);
       }
       bool new_sect = false;
@@ -250,7 +268,7 @@ void hist2_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
         cu.ep = cu.sp + 4;
         cu.sp += 4 + slen;
         new_sect = true;
-        if (stype == 1 && cu.e_local >= 0) cu.C_b += cu.val_b;
+        if (!IS_LAST && stype == 1 && cu.e_local >= 0) cu.C_b += cu.val_b;
       } else {
         cu.ep += 2 + cu.elen;
       }
@@ -260,15 +278,15 @@ void hist2_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
       cu.e_global++;
       cu.sect_first = new_sect;
       cu.decoded = false;
-      if (HFUNC == 1) decode_cur(cu);         // sum mode: full prefix
+      if (HFUNC == H2_SUM) decode_cur(cu);    // sum mode: full prefix
       else if (new_sect) decode_cur(cu);      // section base always decoded
-      else if (cu.sect_left == 0 && cu.e_local + 1 < cu.nrows &&
+      else if (!IS_LAST && cu.sect_left == 0 && cu.e_local + 1 < cu.nrows &&
                staged_byte(cu, cu.sp + 3) == 1)
         decode_cur(cu);   // section last feeds the NEXT section's TypeDrop
                           // correction — peek its type byte and decode only
                           // then (drops are rare; the chunk seam decodes its
                           // own last element unconditionally in step())
-      if (cu.e_local == 0) {
+      if (!IS_LAST && cu.e_local == 0) {
         // first element of a chunk: boundary drop detection
         // (Histogram.compare top-bucket-down, Histogram.scala:204-214)
         if (cu.c > 0) {
@@ -290,11 +308,17 @@ void hist2_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
     S.e_global = -1; E.e_global = -1;
     S.C_b = 0; E.C_b = 0;
     S.psum_b = 0; E.psum_b = 0;
-    open_chunk(S, 0, tsS_all[wave]);
-    if (S.nrows == 0) continue;
-    if (!step(S, tsS_all[wave])) continue;
-    open_chunk(E, 0, tsE_all[wave]);
-    step(E, tsE_all[wave]);
+    if (IS_LAST) {        // E alone: S is never opened or stepped
+      open_chunk(E, 0, tsE_all[wave]);
+      if (E.nrows == 0) continue;
+      if (!step(E, tsE_all[wave])) continue;
+    } else {
+      open_chunk(S, 0, tsS_all[wave]);
+      if (S.nrows == 0) continue;
+      if (!step(S, tsS_all[wave])) continue;
+      open_chunk(E, 0, tsE_all[wave]);
+      step(E, tsE_all[wave]);
+    }
     bool s_more = true;
 
     for (int w = 0; w < num_windows; w++) {
@@ -309,6 +333,27 @@ void hist2_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
         else break;
         if (nxt > wEnd) break;
         if (!step(E, tsE_all[wave])) break;
+      }
+      if (IS_LAST) {
+        // E sits on element 0 with ts > wEnd until the first sample is reached
+        const int64_t t2 = tsE_all[wave][E.e_local];
+        if (t2 > wEnd || t2 < wStart) continue; // empty window
+        decode_cur(E);
+        const size_t cell = (size_t)grp * num_windows + w;
+        if ((out_max || out_min) && lane == 0 && max_off[first + E.c] != 0) {
+          // companion values at the E row only
+          DVec xv, nv;
+          d_vec_open_wide(blob + max_off[first + E.c], &xv, nullptr);
+          d_vec_open_wide(blob + min_off[first + E.c], &nv, nullptr);
+          const double emax = d_dv_at(&xv, E.e_local);
+          const double emin = d_dv_at(&nv, E.e_local);
+          if (out_max && !isnan(emax)) atomic_min_max_f64(&out_max[cell], emax, false);
+          if (out_min && !isnan(emin)) atomic_min_max_f64(&out_min[cell], emin, true);
+        }
+        if (abl & 1) continue;
+        if (live) atomicAdd(&out_sums[cell * nb + b], E.val_b);
+        if (lane == 0) atomicAdd(&out_cnt[cell], 1.0);
+        continue;
       }
       // S → first element with ts >= wStart
       while (s_more && tsS_all[wave][S.e_local] < wStart) {
@@ -346,7 +391,7 @@ void hist2_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
           if (out_min && !isnan(wmin)) atomic_min_max_f64(&out_min[cell], wmin, true);
         }
       }
-      if (HFUNC == 0) {
+      if (IS_RATE) {
         if (!(t2 > t1)) continue;             // highestTime > lowestTime rule
         // paired decode: issue both cursors' stage loads together and let the
         // two (independent) header-parse chains interleave — the per-element
@@ -373,8 +418,17 @@ void hist2_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
           // per-window CorrectionMeta starts NoCorrection there
           double v1 = S.val_b + (S.C_b - S.Centry_b);
           double v2 = E.val_b + (E.C_b - S.Centry_b);
-          double r = d_extrapolated_rate(wStart, wEnd, numSamples,
-                                         t1, v1, t2, v2, true, true);
+          // increase is d_extrapolated_rate(..., isRate = false), spelled as
+          // its core: a second caller with another isRate keeps the compiler
+          // from folding the constant into the shared wrapper, and the rate
+          // instantiations then schedule differently than before
+          double r = HFUNC == H2_RATE
+              ? d_extrapolated_rate(wStart, wEnd, numSamples,
+                                    t1, v1, t2, v2, true, true)
+              : d_extrapolate_core(d_div1000((double)(t1 - wStart)),
+                                   d_div1000((double)(wEnd - t2)),
+                                   d_div1000((double)(t2 - t1)),
+                                   numSamples, v1, v2, true);
           atomicAdd(&out_sums[cell * nb + b], r);
         }
         if (lane == 0) atomicAdd(&out_cnt[cell], 1.0);
@@ -415,9 +469,11 @@ int32_t fdb_launch_hist2(hipStream_t stream, const uint8_t* blob, DirSoA dir,
   const bool w4 = hw && atoi(hw) == 4;         // 5 waves/SIMD measured best
   const char* ab = getenv("FDB_HIST_ABLATE");  // 1=skip emits, 2=skip decodes, 8=phase split
   const int abl = ab ? atoi(ab) : 0;
-  const auto kernel = hfunc == 1 ? hist2_kernel<4, 1>
-                      : w4       ? hist2_kernel<4, 0>
-                                 : hist2_kernel<5, 0>;
+  const auto kernel = hfunc == H2_SUM        ? hist2_kernel<4, H2_SUM>
+                      : hfunc == H2_INCREASE ? hist2_kernel<5, H2_INCREASE>
+                      : hfunc == H2_LAST     ? hist2_kernel<4, H2_LAST>
+                      : w4                   ? hist2_kernel<4, H2_RATE>
+                                             : hist2_kernel<5, H2_RATE>;
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(H2_WAVES * 64), 0, stream,
                      blob, dir, max_off, min_off, series_first, series_nchunks,
                      group_ids, num_series, qstart, qstep, qwindow, num_windows,

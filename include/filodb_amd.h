@@ -139,7 +139,10 @@ int32_t fdb_nibblepack_pack_doubles(const double* in, int32_t n, uint8_t* out, i
 /* Range functions: the dispatch table of RangeFunction.generatorFor
  * (query/.../rangefn/RangeFunction.scala:294-410). */
 #define FDB_FN_RATE             0   /* ChunkedRateFunction       */
-#define FDB_FN_INCREASE         1   /* ChunkedIncreaseFunction   */
+#define FDB_FN_INCREASE         1   /* ChunkedIncreaseFunction; on a histogram dataset
+                                       HistIncreaseFunction (RateFunctions.scala:415-418):
+                                       FDB_FN_HIST_RATE's walk with the extrapolated
+                                       delta left unscaled; no max/min outputs */
 #define FDB_FN_DELTA            2   /* ChunkedDeltaFunction      */
 #define FDB_FN_SUM_OVER_TIME    3
 #define FDB_FN_COUNT_OVER_TIME  4
@@ -155,7 +158,12 @@ int32_t fdb_nibblepack_pack_doubles(const double* in, int32_t n, uint8_t* out, i
                                        raw value of the last sample <= wEnd within the window
                                        (NaN stale markers propagate); the reference uses
                                        window = stale-sample-after + 1 = 300001ms for raw
-                                       queries (PeriodicSamplesMapper.scala:79-81) */
+                                       queries (PeriodicSamplesMapper.scala:79-81).
+                                       On a histogram dataset LastSampleChunkedFunctionH
+                                       (RangeFunction.scala:630-641): the raw buckets of that
+                                       sample, no counter correction; with max/min outputs
+                                       (LastSampleChunkedFunctionHMax, :643-682) the
+                                       companion values at that row */
 #define FDB_FN_PRESENT         13   /* PresentOverTimeChunkedFunctionD
                                        (RangeFunction.scala:725-745): 1 for a non-NaN last
                                        sample; NaN stale markers step back one row */
@@ -314,7 +322,11 @@ int32_t fdb_series_append_hist_mm(fdb_store_t* s, int32_t sid,
  * (merged across series with maxIgnoreNaN/minIgnoreNaN per
  *  HistMaxMinSumAggregator). func_id FDB_FN_HIST_RATE = counter-corrected
  * rate + min/max; FDB_FN_SUM_OVER_TIME = SumOverTime of the histograms
- * (SumAndMaxOverTimeFuncHD shape). out_max/out_min may be NULL. */
+ * (SumAndMaxOverTimeFuncHD shape); FDB_FN_LAST = the last sample's buckets
+ * with the companion values at its row. FDB_FN_INCREASE has no max/min form
+ * (the reference maps only Rate to RateAndMinMaxOverTime,
+ * RangeFunction.scala:383-385): FDB_ERR_BADARG with out_max/out_min.
+ * out_max/out_min may be NULL. */
 /* ------------------------------------------------------------------ */
 /* BinaryRecord v2 ingestion containers (layouts restated
  * from core/.../binaryrecord2/RecordContainer.scala:15-27,
@@ -414,11 +426,57 @@ int32_t fdb_query_exec_hist_mm(fdb_engine_t* e, const fdb_dataset_t* d,
  * out_counts:      [num_groups × windows] contributing-series counts; may be NULL.
  * out_quantile:    [num_groups × windows] quantile(param) of the summed rate
  *                  histogram (NaN where no contributions); may be NULL.
+ * func_id: FDB_FN_HIST_RATE, FDB_FN_INCREASE (increase(hist[window])),
+ * FDB_FN_SUM_OVER_TIME or FDB_FN_LAST (the default instant selector: the
+ * sums are then the groups' summed last samples); anything else is
+ * FDB_ERR_BADARG. The other present steps: fdb_query_exec_hist_present.
  * Round-1 engine limit: one chunk per series per query span. */
 int32_t fdb_query_exec_hist(fdb_engine_t* e, const fdb_dataset_t* d,
                             const fdb_query_t* q, int32_t num_buckets,
                             double* out_bucket_sums, double* out_counts,
                             double* out_quantile, int32_t out_on_device);
+
+/* Histogram present steps (instant functions on a histogram column,
+ * InstantFunction.scala:114-119,362-454) over a geometric scheme,
+ * top(b) = bucket_first * bucket_mult^b: interpolation is linear and no top
+ * is +Inf. p0/p1 are the function's scalar parameters. A cell with
+ * count == 0 is the reference's empty histogram: NaN in every mode. */
+#define FDB_HP_QUANTILE         0  /* Histogram.quantile(p0) (Histogram.scala:65-108):
+                                      the out_quantile rule of fdb_query_exec_hist */
+#define FDB_HP_QUANTILE_MINMAX  1  /* quantile(p0, min, max), HistogramQuantileWithMaxMinImpl:
+                                      the chosen bucket's start/end move to min/max
+                                      when they lie in (start, end]; NaN clips nothing */
+#define FDB_HP_MAX_QUANTILE     2  /* quantile(p0, 0, max), HistogramMaxQuantileImpl */
+#define FDB_HP_BUCKET           3  /* HistogramBucketImpl: value of the first bucket with
+                                      |top - p0| <= 1e-10, else NaN; p0 = +Inf is
+                                      FDB_ERR_BADARG (the reference throws) */
+#define FDB_HP_FRACTION         4  /* histogramFraction(p0, p1) (Histogram.scala:119-197);
+                                      !(p0 >= 0 && p1 >= 0) is FDB_ERR_BADARG */
+#define FDB_HP_FRACTION_MINMAX  5  /* histogramFraction(p0, p1, min, max) */
+
+/* Standalone presenter over caller grids — what a multi-GPU caller runs after
+ * all-reducing the bucket sums. bucket_sums [cells × num_buckets], counts
+ * [cells], out [cells]; maxs/mins [cells] are read by modes 1, 2 and 5 only
+ * (FDB_ERR_BADARG without them) and may be NULL otherwise. All pointers are
+ * host pointers (on_device=0) or all device pointers (on_device=1). */
+int32_t fdb_hist_present(fdb_engine_t* e, int32_t present_id, double p0, double p1,
+                         const double* bucket_sums, const double* counts,
+                         const double* maxs, const double* mins,
+                         int64_t cells, int32_t num_buckets,
+                         double bucket_first, double bucket_mult,
+                         double* out, int32_t on_device);
+
+/* Scan plus present in one call: fdb_query_exec_hist_mm's scan, then the
+ * present step with p0 = q->param, p1 = q->param2 and the dataset's bucket
+ * scheme into out_present [num_groups × windows]. Modes 1, 2 and 5 need a
+ * dataset with companion columns; out_bucket_sums/out_counts/out_max/out_min
+ * may each be NULL. The arguments are checked before the scan runs. */
+int32_t fdb_query_exec_hist_present(fdb_engine_t* e, const fdb_dataset_t* d,
+                                    const fdb_query_t* q, int32_t nb,
+                                    int32_t present_id,
+                                    double* out_bucket_sums, double* out_counts,
+                                    double* out_max, double* out_min,
+                                    double* out_present, int32_t out_on_device);
 
 /* Timing variant for bench.py: runs the same launch `iters` times and returns the
  * average per-iteration kernel milliseconds measured with HIP events on the
