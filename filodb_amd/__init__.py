@@ -369,9 +369,8 @@ class Engine:
         nw = q.num_windows
         if out is None:
             out = np.empty(dataset.num_series * nw, dtype=np.float64)
-        ptr = (out.ctypes.data_as(_c_double_p) if isinstance(out, np.ndarray)
-               else ctypes.cast(out.data_ptr(), _c_double_p))
-        _check(lib().fdb_query_exec_avg_sc(self._h, dataset._h, q, ptr,
+        _check(lib().fdb_query_exec_avg_sc(self._h, dataset._h, ctypes.byref(q),
+                                           _as_f64_ptr(out),
                                            1 if on_device else 0), "avg_sc")
         return out
 

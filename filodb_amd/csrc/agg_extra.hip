@@ -191,42 +191,17 @@ __global__ void agg_present_kernel(double* out, const double* cnt, const double*
   }
 }
 
-// quantile present step (Histogram.quantile, Histogram.scala:63-108; geometric)
-__global__ void hist_quantile_kernel(const double* __restrict__ sums,
-                                     const double* __restrict__ cnt,
-                                     double* __restrict__ out,
-                                     size_t cells, int nb, double q,
-                                     double first, double mult) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= cells) return;
-  if (!(cnt[i] > 0)) { out[i] = NAN; return; }
-  const double* v = sums + i * nb;
-  double top = v[nb - 1];
-  if (q < 0) { out[i] = -INFINITY; return; }
-  if (q > 1) { out[i] = INFINITY; return; }
-  if (nb < 2 || !(top > 0)) { out[i] = NAN; return; }
-  double rank = q * top;
-  int bucket = 0;
-  while (v[bucket] < rank) bucket++;
-  double bucketStart = bucket == 0 ? 0 : first * pow(mult, bucket - 1);
-  double bucketEnd = first * pow(mult, bucket);
-  if (bucket == nb - 1 && isinf(bucketEnd)) { out[i] = first * pow(mult, nb - 2); return; }
-  if (bucket == 0 && first <= 0) { out[i] = first; return; }
-  double count = bucket == 0 ? v[0] : v[bucket] - v[bucket - 1];
-  rank -= bucket == 0 ? 0 : v[bucket - 1];
-  out[i] = bucketStart + (bucketEnd - bucketStart) * (rank / count);
-}
-
 // --- histogram present step, every mode (FDB_HP_*) ---------------------------
-// One thread per cell over a geometric scheme: top(b) = first * pow(mult, b),
-// the expression hist_quantile_kernel uses, so FDB_HP_QUANTILE returns its
-// bits. A geometric scheme is never Base2ExpHistogramBuckets: interpolation is
+// One thread per cell over a geometric scheme: top(b) = first * pow(mult, b).
+// A geometric scheme is never Base2ExpHistogramBuckets: interpolation is
 // linear and no top is +Inf.
 
 // Histogram.quantile(q, min, max) (Histogram.scala:65-108). clip = false is
-// hist_quantile_kernel's rule (no min/max step). The firstBucketGTE walk stops
-// at nb - 1, so a NaN sum cannot leave the cell; the reference's unbounded
-// walk ends there too for valid input (rank <= top).
+// the plain Histogram.quantile(q) (no min/max step): the one implementation
+// behind out_quantile and FDB_HP_QUANTILE, so the two return the same bits.
+// The firstBucketGTE walk stops at nb - 1, so a NaN sum cannot leave the
+// cell; the reference's unbounded walk ends there too for valid input
+// (passing bucket nb - 1 needs top < q * top with 0 <= q <= 1 and top > 0).
 __device__ double hp_quantile(const double* __restrict__ v, int nb, double q,
                               double first, double mult, bool clip,
                               double mn, double mx) {
@@ -344,34 +319,24 @@ __global__ void avg_div_kernel(double* __restrict__ out,
 // ---------------------------------------------------------------------------
 // host-side launchers (prototypes in engine_internal.h)
 // ---------------------------------------------------------------------------
-static int32_t launched(const char* kernel) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    fdb_set_error("%s launch failed: %s", kernel, hipGetErrorString(e));
-    return FDB_ERR;
-  }
-  return FDB_OK;
-}
-
 // one thread per element, 256-thread blocks
 static dim3 blocks256(size_t n) { return dim3((uint32_t)((n + 255) / 256)); }
 
 int32_t fdb_launch_group_reduce(hipStream_t stream, const double* grid,
-                                const int32_t* sbg, const int32_t* goff,
-                                int ng, int nw, int agg_id,
+                                const DatasetView& v, const WindowGrid& w,
+                                int ng, int agg_id,
                                 double* out, double* cnt, double* sq) {
-  hipLaunchKernelGGL(group_reduce_kernel, blocks256((size_t)ng * nw), dim3(256),
-                     0, stream, grid, sbg, goff, ng, nw, agg_id, out, cnt, sq);
-  return launched("group_reduce_kernel");
+  hipLaunchKernelGGL(group_reduce_kernel, blocks256((size_t)ng * w.n), dim3(256),
+                     0, stream, grid, v.sbg, v.goff, ng, w.n, agg_id, out, cnt, sq);
+  return fdb_launched("group_reduce_kernel");
 }
 
 int32_t fdb_launch_topk(hipStream_t stream, const double* grid,
-                        const int32_t* sbg, const int32_t* goff,
-                        int ng, int nw, int k, int top,
-                        double* out, double* ids) {
-  hipLaunchKernelGGL(topk_kernel, blocks256((size_t)ng * nw), dim3(256), 0,
-                     stream, grid, sbg, goff, ng, nw, k, top, out, ids);
-  return launched("topk_kernel");
+                        const DatasetView& v, const WindowGrid& w,
+                        int ng, int k, int top, double* out, double* ids) {
+  hipLaunchKernelGGL(topk_kernel, blocks256((size_t)ng * w.n), dim3(256), 0,
+                     stream, grid, v.sbg, v.goff, ng, w.n, k, top, out, ids);
+  return fdb_launched("topk_kernel");
 }
 
 int32_t fdb_launch_agg_present(hipStream_t stream, double* out,
@@ -379,15 +344,7 @@ int32_t fdb_launch_agg_present(hipStream_t stream, double* out,
                                size_t n, int agg_id, int partial) {
   hipLaunchKernelGGL(agg_present_kernel, blocks256(n), dim3(256), 0, stream,
                      out, cnt, sq, n, agg_id, partial);
-  return launched("agg_present_kernel");
-}
-
-int32_t fdb_launch_hist_quantile(hipStream_t stream, const double* sums,
-                                 const double* cnt, double* out, size_t cells,
-                                 int nb, double q, double first, double mult) {
-  hipLaunchKernelGGL(hist_quantile_kernel, blocks256(cells), dim3(256), 0,
-                     stream, sums, cnt, out, cells, nb, q, first, mult);
-  return launched("hist_quantile_kernel");
+  return fdb_launched("agg_present_kernel");
 }
 
 bool fdb_hist_present_needs_mm(int present_id) {
@@ -432,39 +389,39 @@ int32_t fdb_launch_hist_present(hipStream_t stream, const double* sums,
   hipLaunchKernelGGL(hist_present_kernel, blocks256(cells), dim3(256), 0,
                      stream, sums, cnt, maxs, mins, out, cells, nb, present_id,
                      p0, p1, first, mult);
-  return launched("hist_present_kernel");
+  return fdb_launched("hist_present_kernel");
 }
 
 int32_t fdb_launch_avg_div(hipStream_t stream, double* out, const double* a,
                            const double* b, size_t n) {
   hipLaunchKernelGGL(avg_div_kernel, blocks256(n), dim3(256), 0, stream,
                      out, a, b, n);
-  return launched("avg_div_kernel");
+  return fdb_launched("avg_div_kernel");
 }
 
 int32_t fdb_launch_quantile_cells(hipStream_t stream, const double* grid,
-                                  const int32_t* sbg, const int32_t* goff,
-                                  int ng, int nw, double q, double* out) {
-  size_t cells = (size_t)ng * nw;
+                                  const DatasetView& v, const WindowGrid& w,
+                                  int ng, double q, double* out) {
+  size_t cells = (size_t)ng * w.n;
   hipLaunchKernelGGL(quantile_cell_kernel,
                      dim3((uint32_t)((cells + 63) / 64)), dim3(64), 0, stream,
-                     grid, sbg, goff, ng, nw, q, out);
-  return launched("quantile_cell_kernel");
+                     grid, v.sbg, v.goff, ng, w.n, q, out);
+  return fdb_launched("quantile_cell_kernel");
 }
 
 int32_t fdb_launch_count_values(hipStream_t stream, const double* grid,
-                                const int32_t* sbg, const int32_t* goff,
-                                int ng, int nw, int k_cap,
+                                const DatasetView& v, const WindowGrid& w,
+                                int ng, int k_cap,
                                 double* out_vals, double* out_cnts,
                                 int32_t* out_n, int32_t* overflow) {
   if (k_cap < 1 || k_cap > CV_CAP) {
     fdb_set_error("count_values k_cap %d out of range 1..%d", k_cap, CV_CAP);
     return FDB_ERR_BADARG;
   }
-  size_t cells = (size_t)ng * nw;
+  size_t cells = (size_t)ng * w.n;
   hipLaunchKernelGGL(count_values_kernel,
                      dim3((uint32_t)((cells + 63) / 64)), dim3(64), 0, stream,
-                     grid, sbg, goff, ng, nw, k_cap, out_vals, out_cnts,
+                     grid, v.sbg, v.goff, ng, w.n, k_cap, out_vals, out_cnts,
                      out_n, overflow);
-  return launched("count_values_kernel");
+  return fdb_launched("count_values_kernel");
 }

@@ -1,13 +1,14 @@
 // Declarations shared by the library's translation units and by nothing
 // outside csrc/: the error sink, the engine's stream accessor, the HIP error
-// macros, owning wrappers for device memory and events, and every kernel
-// launcher's prototype. Each defining file includes this header, so a
+// macros, owning wrappers for device memory, output grids and events, the
+// dataset view and window grid, and every kernel launcher's prototype. Each defining file includes this header, so a
 // signature that drifts from its declaration is a compile error.
 #ifndef FDB_ENGINE_INTERNAL_H
 #define FDB_ENGINE_INTERNAL_H
 
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <cstdlib>
 
 #include "chunk_format.h"
 #include "scan_common.h"
@@ -21,6 +22,23 @@ hipStream_t fdb_engine_stream(fdb_engine_t* e);   // engine.hip
   fdb_set_error("%s failed: %s", #expr, hipGetErrorString(_e)); return FDB_ERR; } } while (0)
 #define HIP_CHECK_NULL(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { \
   fdb_set_error("%s failed: %s", #expr, hipGetErrorString(_e)); return nullptr; } } while (0)
+
+// after a kernel launch: the launch error, if any, named after the kernel
+inline int32_t fdb_launched(const char* kernel) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    fdb_set_error("%s launch failed: %s", kernel, hipGetErrorString(e));
+    return FDB_ERR;
+  }
+  return FDB_OK;
+}
+
+// integer knob from the environment, read afresh at every call: the tests flip
+// these between two queries of one process
+inline int fdb_env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
 
 // Device buffer that is freed on every exit of the scope that holds it. It
 // either owns an allocation (alloc) or wraps memory that belongs to someone
@@ -45,6 +63,15 @@ class DevPtr {
     owned_ = true;
     return true;
   }
+  // allocates count elements plus tail_pad_bytes zeroed bytes and copies src
+  // in; zero bytes still allocates 8, so an empty table has a real address
+  bool upload(const T* src, size_t count, size_t tail_pad_bytes = 0) {
+    const size_t bytes = count * sizeof(T), total = bytes + tail_pad_bytes;
+    if (!alloc(total ? total : 8)) return false;
+    if (tail_pad_bytes &&
+        hipMemset((char*)p_ + bytes, 0, tail_pad_bytes) != hipSuccess) return false;
+    return hipMemcpy(p_, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+  }
   void wrap(T* p) { reset(); p_ = p; }
   void reset() {
     if (owned_) (void)hipFree(p_);
@@ -58,6 +85,31 @@ class DevPtr {
   bool owned_ = false;
 };
 using DevBuf = DevPtr<double>;
+
+// One output grid of n elements that a caller passed as `user`: the caller's
+// own device memory when on_device, else a device buffer of ours that fetch()
+// copies back to the host pointer. A null `user` is a grid the call needs but
+// the caller did not ask for. alloc() is separate so that an optional grid
+// costs nothing until the entry point decides it exists.
+template <typename T>
+class OutGrid {
+ public:
+  OutGrid(T* user, bool on_device, size_t n)
+      : user_(on_device ? nullptr : user), n_(n) { if (on_device) dev_.wrap(user); }
+  bool alloc() { return dev_ || dev_.alloc(n_ * sizeof(T)); }
+  T* get() const { return dev_.get(); }
+  explicit operator bool() const { return (bool)dev_; }
+  hipError_t fetch() const {
+    if (!user_ || !dev_) return hipSuccess;
+    return hipMemcpy(user_, dev_.get(), n_ * sizeof(T), hipMemcpyDeviceToHost);
+  }
+
+ private:
+  DevPtr<T> dev_;
+  T* user_;      // host destination of fetch(), null when there is none
+  size_t n_;
+};
+using OutBuf = OutGrid<double>;
 
 // hipEvent_t destroyed on scope exit
 class DevEvent {
@@ -90,71 +142,65 @@ inline bool fdb_scan_supported(int func_id) {
   }
 }
 
+// What the kernels read of an uploaded dataset (device pointers) and a query's
+// window grid. Host-side only: every launcher unpacks them into its kernel's
+// own arguments.
+struct DatasetView {
+  const uint8_t* blob;
+  DirSoA dir;
+  const uint64_t *max_off, *min_off;   // hist companion columns (0 = absent)
+  const int32_t *series_first, *series_nchunks, *group_ids;
+  const int32_t *sbg, *goff;           // group-sorted series index
+  int num_series;
+};
+struct WindowGrid { int64_t start, step, end, window; int n; };
+
 // scan_fast.hip: single-chunk-per-series fast path
 struct FdbFastDesc;   // fast_desc.h: one decode descriptor per series
 #define FDB_FAST_SAMPLE 256   // host-side descriptor sample kept per dataset
-int32_t fdb_launch_fast_scan(hipStream_t stream, const uint8_t* blob,
+int32_t fdb_launch_fast_scan(hipStream_t stream, const DatasetView& v,
                              const FdbFastDesc* desc,
                              const FdbFastDesc* sample, int nsample,   // host
-                             const int32_t* group_ids, const int32_t* series_by_group,
-                             int num_series,
-                             int64_t qstart, int64_t qstep, int64_t qwindow,
-                             int num_windows, int func_id, int agg_id, int emit_group,
-                             double* out, double* out_cnt, double* out_sq,
-                             int phase_mask);
+                             const WindowGrid& w, int func_id, int agg_id,
+                             int emit_group, double* out, double* out_cnt,
+                             double* out_sq, int phase_mask);
 
 // scan_stream.hip: unbounded multi-chunk general path (chunk summaries +
 // per-window walk)
 int32_t fdb_launch_summaries(hipStream_t stream, const uint8_t* blob, DirSoA dir,
                              int64_t num_chunks, void* sums);
 int64_t fdb_chunksum_bytes(int64_t num_chunks);
-int32_t fdb_launch_stream_walk(hipStream_t stream, const uint8_t* blob,
-                               DirSoA dir, const void* sums,
-                               const int32_t* series_first,
-                               const int32_t* series_nchunks, int num_series,
-                               int64_t qstart, int64_t qstep, int64_t qend,
-                               int64_t qwindow, int num_windows, int func_id,
-                               double* out);
+int32_t fdb_launch_stream_walk(hipStream_t stream, const DatasetView& v,
+                               const void* sums, const WindowGrid& w,
+                               int func_id, double* out);
 
 // window_sample.hip: per-(series,window) sample-buffer functions (FN 16-18,
 // holt_winters, deriv)
 bool fdb_window_sample_supported(int func_id);
-int32_t fdb_launch_window_sample(hipStream_t stream, const uint8_t* blob,
-                                 DirSoA dir, const int32_t* series_first,
-                                 const int32_t* series_nchunks, int num_series,
-                                 int64_t qstart, int64_t qstep, int64_t qwindow,
-                                 int num_windows, int func_id, double param,
+int32_t fdb_launch_window_sample(hipStream_t stream, const DatasetView& v,
+                                 const WindowGrid& w, int func_id, double param,
                                  double param2, double* out, int32_t* overflow);
 
 // hist2.hip: two-cursor histogram walk (unbounded chunks / window ratio).
 // hfunc is the walk's window function.
 enum { H2_RATE = 0, H2_SUM = 1, H2_INCREASE = 2, H2_LAST = 3 };
-int32_t fdb_launch_hist2(hipStream_t stream, const uint8_t* blob, DirSoA dir,
-                         const uint64_t* max_off, const uint64_t* min_off,
-                         const int32_t* series_first,
-                         const int32_t* series_nchunks,
-                         const int32_t* group_ids, int num_series,
-                         int64_t qstart, int64_t qstep, int64_t qwindow,
-                         int num_windows, int nb, int hfunc,
+int32_t fdb_launch_hist2(hipStream_t stream, const DatasetView& v,
+                         const WindowGrid& w, int nb, int hfunc,
                          double* out_sums, double* out_cnt,
                          double* out_max, double* out_min);
 
-// agg_extra.hip: presenters over the per-series [S×W] grid or the [G×W]
-// aggregate grids. sbg/goff are the dataset's group-sorted series index.
+// agg_extra.hip: presenters over the per-series [S×W] grid (folded along the
+// view's group-sorted index into ng groups) or the [G×W] aggregate grids
 int32_t fdb_launch_group_reduce(hipStream_t stream, const double* grid,
-                                const int32_t* sbg, const int32_t* goff,
-                                int ng, int nw, int agg_id,
+                                const DatasetView& v, const WindowGrid& w,
+                                int ng, int agg_id,
                                 double* out, double* cnt, double* sq);
 int32_t fdb_launch_topk(hipStream_t stream, const double* grid,
-                        const int32_t* sbg, const int32_t* goff,
-                        int ng, int nw, int k, int top,
-                        double* out, double* ids);
+                        const DatasetView& v, const WindowGrid& w,
+                        int ng, int k, int top, double* out, double* ids);
 int32_t fdb_launch_agg_present(hipStream_t stream, double* out,
                                const double* cnt, const double* sq,
                                size_t n, int agg_id, int partial);
-int32_t fdb_launch_hist_quantile(hipStream_t stream, const double* sums,
-                                 const double* cnt, double* out, size_t cells,
-                                 int nb, double q, double first, double mult);
 // histogram present step over [cells × nb] sums (FDB_HP_*; maxs/mins nullable).
 // The launcher runs fdb_hist_present_check itself; an entry point that scans
 // first calls it before the scan.
@@ -169,11 +215,11 @@ int32_t fdb_launch_hist_present(hipStream_t stream, const double* sums,
 int32_t fdb_launch_avg_div(hipStream_t stream, double* out, const double* a,
                            const double* b, size_t n);
 int32_t fdb_launch_quantile_cells(hipStream_t stream, const double* grid,
-                                  const int32_t* sbg, const int32_t* goff,
-                                  int ng, int nw, double q, double* out);
+                                  const DatasetView& v, const WindowGrid& w,
+                                  int ng, double q, double* out);
 int32_t fdb_launch_count_values(hipStream_t stream, const double* grid,
-                                const int32_t* sbg, const int32_t* goff,
-                                int ng, int nw, int k_cap,
+                                const DatasetView& v, const WindowGrid& w,
+                                int ng, int k_cap,
                                 double* out_vals, double* out_cnts,
                                 int32_t* out_n, int32_t* overflow);
 

@@ -452,36 +452,26 @@ void hist2_kernel(const uint8_t* __restrict__ blob, DirSoA dir,
   }
 }
 
-int32_t fdb_launch_hist2(hipStream_t stream, const uint8_t* blob, DirSoA dir,
-                         const uint64_t* max_off, const uint64_t* min_off,
-                         const int32_t* series_first,
-                         const int32_t* series_nchunks,
-                         const int32_t* group_ids, int num_series,
-                         int64_t qstart, int64_t qstep, int64_t qwindow,
-                         int num_windows, int nb, int hfunc,
+int32_t fdb_launch_hist2(hipStream_t stream, const DatasetView& v,
+                         const WindowGrid& w, int nb, int hfunc,
                          double* out_sums, double* out_cnt,
                          double* out_max, double* out_min) {
-  int grid = (num_series + H2_WAVES - 1) / H2_WAVES;
-  int cap = 8192;
-  if (const char* g = getenv("FDB_HIST_GRID")) cap = atoi(g);
+  int grid = (v.num_series + H2_WAVES - 1) / H2_WAVES;
+  const int cap = fdb_env_int("FDB_HIST_GRID", 8192);
   if (cap > 0 && grid > cap) grid = cap;
-  const char* hw = getenv("FDB_HIST_WAVES");   // occupancy experiment knob
-  const bool w4 = hw && atoi(hw) == 4;         // 5 waves/SIMD measured best
-  const char* ab = getenv("FDB_HIST_ABLATE");  // 1=skip emits, 2=skip decodes, 8=phase split
-  const int abl = ab ? atoi(ab) : 0;
+  // occupancy experiment knob; 5 waves/SIMD measured best
+  const bool w4 = fdb_env_int("FDB_HIST_WAVES", 0) == 4;
+  // 1=skip emits, 2=skip decodes, 8=phase split
+  const int abl = fdb_env_int("FDB_HIST_ABLATE", 0);
   const auto kernel = hfunc == H2_SUM        ? hist2_kernel<4, H2_SUM>
                       : hfunc == H2_INCREASE ? hist2_kernel<5, H2_INCREASE>
                       : hfunc == H2_LAST     ? hist2_kernel<4, H2_LAST>
                       : w4                   ? hist2_kernel<4, H2_RATE>
                                              : hist2_kernel<5, H2_RATE>;
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(H2_WAVES * 64), 0, stream,
-                     blob, dir, max_off, min_off, series_first, series_nchunks,
-                     group_ids, num_series, qstart, qstep, qwindow, num_windows,
-                     nb, out_sums, out_cnt, out_max, out_min, abl);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    fdb_set_error("hist2_kernel launch failed: %s", hipGetErrorString(e));
-    return FDB_ERR;
-  }
-  return FDB_OK;
+                     v.blob, v.dir, v.max_off, v.min_off, v.series_first,
+                     v.series_nchunks, v.group_ids, v.num_series, w.start,
+                     w.step, w.window, w.n, nb, out_sums, out_cnt, out_max,
+                     out_min, abl);
+  return fdb_launched("hist2_kernel");
 }

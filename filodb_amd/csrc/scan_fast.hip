@@ -739,8 +739,7 @@ void fast_scan_kernel(const uint8_t* __restrict__ blob,
 // ---------------------------------------------------------------------------
 struct FastLaunch {   // grid, stream, the kernel's arguments, the build selectors
   int grid; hipStream_t stream;
-  const uint8_t* blob; const FdbFastDesc* desc; const int32_t *group_ids, *sbg;
-  int num_series; int64_t qstart, qstep, qwindow; int num_windows, agg_id;
+  const DatasetView& v; const FdbFastDesc* desc; const WindowGrid& w; int agg_id;
   double *out, *out_cnt, *out_sq;
   int wshare;         // 0: two searches per window
   bool aligned;       // shared search only: the build that holds the direct rows
@@ -758,9 +757,9 @@ static void launch_fast_as(const FastLaunch& a) {
       : a.aligned ? fast_scan_kernel<F, EMIT, MINW, TIMED, true, true>
                   : fast_scan_kernel<F, EMIT, MINW, TIMED, true, false>;
   hipLaunchKernelGGL(kernel, dim3(a.grid), dim3(FAST_WAVES * 64), 0, a.stream,
-                     a.blob, a.desc, a.group_ids, a.sbg, a.num_series, a.qstart,
-                     a.qstep, a.qwindow, a.num_windows, a.agg_id, a.out, a.out_cnt,
-                     a.out_sq, a.wshare);
+                     a.v.blob, a.desc, a.v.group_ids, a.v.sbg, a.v.num_series,
+                     a.w.start, a.w.step, a.w.window, a.w.n, a.agg_id, a.out,
+                     a.out_cnt, a.out_sq, a.wshare);
 }
 template <int F, int MINW>
 static void launch_fast(const FastLaunch& a) {
@@ -775,18 +774,17 @@ static void launch_fast(const FastLaunch& a) {
 static int32_t g_last_aligned = 0;
 extern "C" int32_t fdb_debug_last_fast_aligned(void) { return g_last_aligned; }
 
-int32_t fdb_launch_fast_scan(hipStream_t stream, const uint8_t* blob,
+int32_t fdb_launch_fast_scan(hipStream_t stream, const DatasetView& v,
                              const FdbFastDesc* desc,
                              const FdbFastDesc* sample, int nsample,
-                             const int32_t* group_ids, const int32_t* series_by_group,
-                             int num_series,
-                             int64_t qstart, int64_t qstep, int64_t qwindow,
-                             int num_windows, int func_id, int agg_id, int emit_group,
-                             double* out, double* out_cnt, double* out_sq,
-                             int phase_mask) {
-  int grid = (num_series + FAST_WAVES - 1) / FAST_WAVES;
-  int cap = 16384;      // measured best of {1536, 3072, 8192, 16384}
-  if (const char* g = getenv("FDB_GRID")) cap = atoi(g);   // perf experiments
+                             const WindowGrid& w, int func_id, int agg_id,
+                             int emit_group, double* out, double* out_cnt,
+                             double* out_sq, int phase_mask) {
+  const int64_t qstart = w.start, qstep = w.step, qwindow = w.window;
+  const int num_windows = w.n;
+  int grid = (v.num_series + FAST_WAVES - 1) / FAST_WAVES;
+  // measured best of {1536, 3072, 8192, 16384}; FDB_GRID: perf experiments
+  const int cap = fdb_env_int("FDB_GRID", 16384);
   if (cap > 0 && grid > cap) grid = cap;
   // windows share end searches when the window is m = 1..64 whole steps
   // (FDB_WINDOW_SHARE=0: the two-searches-per-window path, for A/B runs)
@@ -794,7 +792,7 @@ int32_t fdb_launch_fast_scan(hipStream_t stream, const uint8_t* blob,
   if (qstep > 0 && qwindow % qstep == 0 && qwindow / qstep >= 1 &&
       qwindow / qstep <= 64)
     wshare = (int)(qwindow / qstep);
-  if (const char* s = getenv("FDB_WINDOW_SHARE")) { if (atoi(s) == 0) wshare = 0; }
+  if (fdb_env_int("FDB_WINDOW_SHARE", 1) == 0) wshare = 0;
   // The build that also holds the direct rows (ALIGNED) costs a series that
   // does not qualify about 2 % (registers, SGPR spills: profiles/README.md,
   // round 7) and saves one that does about 9 %, so it is launched only where
@@ -817,10 +815,9 @@ int32_t fdb_launch_fast_scan(hipStream_t stream, const uint8_t* blob,
     }
   }
   bool aligned = eligible > 0 && 4 * eligible >= sampled;
-  if (const char* s = getenv("FDB_ALIGNED")) { if (atoi(s) == 0) aligned = false; }
+  if (fdb_env_int("FDB_ALIGNED", 1) == 0) aligned = false;
   g_last_aligned = aligned ? eligible : 0;
-  const FastLaunch a{grid, stream, blob, desc, group_ids, series_by_group,
-                     num_series, qstart, qstep, qwindow, num_windows, agg_id,
+  const FastLaunch a{grid, stream, v, desc, w, agg_id,
                      out, out_cnt, out_sq, wshare, aligned, emit_group != 0,
                      (phase_mask & 8) != 0};   // bit 3: s_memtime phase ablation
   switch (func_id) {     // <function, plain-grid MINW>
@@ -847,10 +844,5 @@ int32_t fdb_launch_fast_scan(hipStream_t stream, const uint8_t* blob,
       fdb_set_error("fast scan: unsupported func_id %d", func_id);
       return FDB_ERR_BADARG;
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    fdb_set_error("fast_scan_kernel launch failed: %s", hipGetErrorString(e));
-    return FDB_ERR;
-  }
-  return FDB_OK;
+  return fdb_launched("fast_scan_kernel");
 }

@@ -401,30 +401,21 @@ int32_t fdb_launch_summaries(hipStream_t stream, const uint8_t* blob, DirSoA dir
   if (grid < 1) grid = 1;
   hipLaunchKernelGGL(summary_kernel, dim3(grid), dim3(256), 0, stream,
                      blob, dir, num_chunks, (ChunkSum*)sums);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    fdb_set_error("summary_kernel launch failed: %s", hipGetErrorString(e));
-    return FDB_ERR;
-  }
-  return FDB_OK;
+  return fdb_launched("summary_kernel");
 }
 
 int64_t fdb_chunksum_bytes(int64_t num_chunks) {
   return num_chunks * (int64_t)sizeof(ChunkSum);
 }
 
-int32_t fdb_launch_stream_walk(hipStream_t stream, const uint8_t* blob,
-                               DirSoA dir, const void* sums,
-                               const int32_t* series_first,
-                               const int32_t* series_nchunks, int num_series,
-                               int64_t qstart, int64_t qstep, int64_t qend,
-                               int64_t qwindow, int num_windows, int func_id,
-                               double* out) {
-  int grid = (num_series + 3) / 4;
+int32_t fdb_launch_stream_walk(hipStream_t stream, const DatasetView& v,
+                               const void* sums, const WindowGrid& w,
+                               int func_id, double* out) {
+  int grid = (v.num_series + 3) / 4;
   if (grid > 8192) grid = 8192;
   if (grid < 1) grid = 1;
-  #define SARGS blob, dir, (const ChunkSum*)sums, series_first, series_nchunks, \
-      num_series, qstart, qstep, qend, qwindow, num_windows, out
+  #define SARGS v.blob, v.dir, (const ChunkSum*)sums, v.series_first, \
+      v.series_nchunks, v.num_series, w.start, w.step, w.end, w.window, w.n, out
   #define SCASE(F) case F: \
     hipLaunchKernelGGL((stream_walk_kernel<F>), dim3(grid), dim3(256), 0, \
                        stream, SARGS); break
@@ -441,10 +432,5 @@ int32_t fdb_launch_stream_walk(hipStream_t stream, const uint8_t* blob,
   }
   #undef SCASE
   #undef SARGS
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    fdb_set_error("stream_walk_kernel launch failed: %s", hipGetErrorString(e));
-    return FDB_ERR;
-  }
-  return FDB_OK;
+  return fdb_launched("stream_walk_kernel");
 }

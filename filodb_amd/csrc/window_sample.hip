@@ -267,20 +267,18 @@ bool fdb_window_sample_supported(int func_id) {
          func_id == FN_DERIV;
 }
 
-int32_t fdb_launch_window_sample(hipStream_t stream, const uint8_t* blob,
-                                 DirSoA dir, const int32_t* series_first,
-                                 const int32_t* series_nchunks, int num_series,
-                                 int64_t qstart, int64_t qstep, int64_t qwindow,
-                                 int num_windows, int func_id, double param,
+int32_t fdb_launch_window_sample(hipStream_t stream, const DatasetView& v,
+                                 const WindowGrid& w, int func_id, double param,
                                  double param2, double* out, int32_t* overflow) {
-  size_t pairs = (size_t)num_series * num_windows;
+  size_t pairs = (size_t)v.num_series * w.n;
   size_t grid = (pairs + WS_WAVES - 1) / WS_WAVES;
   if (grid > 8192) grid = 8192;
   if (grid < 1) grid = 1;
   auto launch = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(WS_WAVES * 64), 0, stream,
-                       blob, dir, series_first, series_nchunks, num_series, qstart,
-                       qstep, qwindow, num_windows, param, param2, out, overflow);
+                       v.blob, v.dir, v.series_first, v.series_nchunks,
+                       v.num_series, w.start, w.step, w.window, w.n, param,
+                       param2, out, overflow);
   };
   switch (func_id) {
     case FN_QUANTILE:       launch(window_sample_kernel<FN_QUANTILE>); break;
@@ -292,10 +290,5 @@ int32_t fdb_launch_window_sample(hipStream_t stream, const uint8_t* blob,
       fdb_set_error("window sample: unsupported func_id %d", func_id);
       return FDB_ERR_BADARG;
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    fdb_set_error("window_sample_kernel launch failed: %s", hipGetErrorString(e));
-    return FDB_ERR;
-  }
-  return FDB_OK;
+  return fdb_launched("window_sample_kernel");
 }

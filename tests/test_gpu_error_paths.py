@@ -76,11 +76,7 @@ def test_query_after_window_sample_overflow(fdb, oracle, engine):
     check(got, want)
 
 
-def test_count_values_after_overflow(fdb, oracle, engine):
-    st, q = count_values_case(fdb)
-    ds = engine.upload(st)
-    with pytest.raises(RuntimeError):
-        engine.count_values(ds, q, k_cap=4)
+def check_count_values(oracle, engine, st, ds, q):
     gv, gc, gn = engine.count_values(ds, q, k_cap=16)
     wv, wc, wn = oracle.count_values(st.view(), q, k_cap=16)
     assert wn.tolist() == [10] * q.num_windows
@@ -88,6 +84,29 @@ def test_count_values_after_overflow(fdb, oracle, engine):
     for i in range(len(wn)):
         check(gv[i][:wn[i]], wv[i][:wn[i]])
         np.testing.assert_array_equal(gc[i][:wn[i]], wc[i][:wn[i]])
+
+
+def test_count_values_after_overflow(fdb, oracle, engine):
+    st, q = count_values_case(fdb)
+    ds = engine.upload(st)
+    with pytest.raises(RuntimeError):
+        engine.count_values(ds, q, k_cap=4)
+    check_count_values(oracle, engine, st, ds, q)
+
+
+def test_count_values_over_sample_overflow(fdb, oracle, engine):
+    """count_values over quantile_over_time whose window overflows the sample
+    buffer: the error is the scan's, not the presenter's distinct-value limit,
+    and the flag the two kernels share is clear afterwards"""
+    st, q_over, _ = sample_overflow_case(fdb)
+    q_over.agg_id, q_over.num_groups = fdb.AGG_COUNT_VALUES, 1
+    ds = engine.upload(st)
+    with pytest.raises(RuntimeError) as ei:
+        engine.count_values(ds, q_over, k_cap=16)
+    assert "sample buffer" in str(ei.value)
+    assert "distinct values" not in str(ei.value)
+    st2, q = count_values_case(fdb)
+    check_count_values(oracle, engine, st2, engine.upload(st2), q)
 
 
 def test_hist_query_after_argument_error(fdb, oracle, engine):

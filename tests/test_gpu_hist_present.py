@@ -217,3 +217,61 @@ def test_quantile_mode_is_out_quantile(fdb, engine, mm_dataset):
         got = present(fdb, engine, fdb.HP_QUANTILE, s, c, nb, 2.0, 2.0, p0=q0)
         assert got.tobytes() == quant.tobytes(), q0
         assert (c > 0).any() and (c == 0).any()
+
+
+@pytest.mark.parametrize("func", ["rate", "last"])
+def test_max_and_min_outputs_are_independent(fdb, engine, mm_dataset, func):
+    """out_min alone, out_max alone and both give the same grids"""
+    ds, start = mm_dataset
+    nb, ng = 8, 4
+    fid = fdb.FN_HIST_RATE if func == "rate" else fdb.FN_LAST
+    q = fdb.make_query(start, 15000, start + 70 * 15000, 120000, fid,
+                       fdb.AGG_SUM, ng)
+    n = ng * q.num_windows
+
+    def run(want_max, want_min):
+        s, c = np.zeros(n * nb), np.zeros(n)
+        mx = np.zeros(n) if want_max else None
+        mn = np.zeros(n) if want_min else None
+        engine.query_hist_mm(ds, q, nb, out_bucket_sums=s, out_counts=c,
+                             out_max=mx, out_min=mn)
+        return s, c, mx, mn
+
+    s0, c0, mx0, mn0 = run(True, True)
+    assert np.isfinite(mx0).any() and np.isfinite(mn0).any()
+    assert np.isnan(mx0).any() and np.isnan(mn0).any()    # the empty windows
+    s1, c1, _, mn1 = run(False, True)
+    s2, c2, mx2, _ = run(True, False)
+    assert mn1.tobytes() == mn0.tobytes()
+    assert mx2.tobytes() == mx0.tobytes()
+    for s, c in ((s1, c1), (s2, c2)):
+        assert s.tobytes() == s0.tobytes() and c.tobytes() == c0.tobytes()
+
+
+def test_scheme_comes_from_the_dataset(fdb, engine):
+    """a 0.5/1.5 scheme: out_quantile presents over the uploaded store's own
+    bucket tops (every other store here is 2.0/2.0)"""
+    rng = np.random.default_rng(17)
+    nb, first, mult = 8, 0.5, 1.5
+    st = fdb.ChunkStore()
+    t0 = None
+    for g in range(2):
+        ts, cum = synth_hist(rng, 30, nb=nb)
+        t0 = int(ts[0]) if t0 is None else t0
+        st.append_hist(st.add_series(g, fdb.COL_HIST), ts, cum, first=first,
+                       mult=mult)
+    st.seal()
+    ds = engine.upload(st)
+    start = t0 - 45000                       # the first windows are empty
+    q = fdb.make_query(start, 15000, start + 25 * 15000, 120000,
+                       fdb.FN_HIST_RATE, fdb.AGG_SUM, 2, param=0.9)
+    n = 2 * q.num_windows
+    s, c, quant = np.zeros(n * nb), np.zeros(n), np.zeros(n)
+    engine.query_hist(ds, q, nb, out_bucket_sums=s, out_counts=c,
+                      out_quantile=quant)
+    want = present(fdb, engine, fdb.HP_QUANTILE, s, c, nb, first, mult, p0=0.9)
+    assert quant.tobytes() == want.tobytes()
+    assert (c == 0).any() and np.isnan(quant[c == 0]).all()
+    assert np.isfinite(quant[c > 0]).mean() > 0.5
+    other = present(fdb, engine, fdb.HP_QUANTILE, s, c, nb, 2.0, 2.0, p0=0.9)
+    assert other.tobytes() != quant.tobytes()
